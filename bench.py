@@ -13,17 +13,25 @@ timed region.  `value`, `ms_per_step`, `roofline` and `roofline.traffic` all bel
 With N > 1 every rank denoises its own clips, one per step (clip-parallel = configs[4] / Config 5, no data-path collective: weak
 scaling) and the value is the whole-job aggregate.
 
-After the timed region the single-GPU run measures a second, separately labelled leg, `throughput_mode`: --throughput-clips
-(4) INDEPENDENT configs[1] clips denoised together (latents [4,4,16,64,64], the batch axis of the reference's own pipeline,
-pipeline_videoswap.py:478-550; cf. configs[4] "throughput mode"), one warm-up + --throughput-steps (3) timed steps with its own
-roofline.  It is never `value`.  --clips-per-step B makes the batch the headline of a run (and says so in `metric`).
+A plain run sets up, warms up, times exactly --steps steps and prints the line; --dump-outputs DIR then also writes what the
+last timed step returned (`videos`, the latents a caller of the pipeline receives) as DIR/<name>.npy in float32, so that two
+builds can be compared output for output on the same seeded weights and inputs.
+
+--full adds everything that the headline does not need:
+  * the roofline of the dominant kernel (vsx_gemm_f16: implicit-GEMM conv + GEMMs, 84 % of the FLOPs), measured live with
+    hipEvents around every --prof-stride-th launch of the timed steps, and the board power / clock over them;
+  * after the timed region, on a single GPU, a second, separately labelled leg, `throughput_mode`: --throughput-clips (4)
+    INDEPENDENT configs[1] clips denoised together (latents [4,4,16,64,64], the batch axis of the reference's own pipeline,
+    pipeline_videoswap.py:478-550; cf. configs[4] "throughput mode"), one warm-up + --throughput-steps (3) timed steps with
+    its own roofline.  It is never `value`.  --clips-per-step B makes the batch the headline of a run (and says so in `metric`);
+  * the CPU baseline (the oracle — a port of the reference's PyTorch path — timed on the host cores on a bounded sample) and
+    the same oracle module in PyTorch-ROCm eager fp16 on the GPU.
 
 Rank 0 prints ONE JSON line: metric value = denoised frames/s end to end (R1e = frames / wall(inversion + sampling)),
-plus R1s / R2 readings, the roofline of the dominant kernel (vsx_gemm_f16: implicit-GEMM conv + GEMMs, 84 % of the
-FLOPs) measured live with hipEvents on the launch stream, and the CPU baseline (the oracle — a port of the
-reference's PyTorch path — timed on the host cores on a bounded sample).
+plus R1s / R2 readings and, with --full, the objects above.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -77,11 +85,16 @@ def parse():
                     help='independent clips denoised TOGETHER in one step of the HEADLINE: latents [B,4,T,h,w], the batch axis of the '
                          'reference\'s own pipeline (pipeline_videoswap.py:478-550) — UNet batch B in the inversion, 2B under CFG.  '
                          'Default 1 = SURVEY.md §8(d) Config 2, the shape the reference\'s test.py drives; B > 1 is a throughput mode '
-                         'and is named in `metric`.  The default run measures B = 4 as its own leg (`throughput_mode`)')
+                         'and is named in `metric`.  A --full run measures B = 4 as its own leg (`throughput_mode`)')
     ap.add_argument('--throughput-clips', type=int, default=4,
                     help='clips per step of the second leg (`throughput_mode`, single-GPU default-config runs only; 0 = skip)')
     ap.add_argument('--throughput-steps', type=int, default=3, help='timed steps of the second leg (after one warm-up step)')
     ap.add_argument('--no-extra-reading', action='store_true', help='skip the `throughput_mode` leg (profiling runs pass it)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the sampled roofline and board power of the timed '
+                         'steps, the `throughput_mode` leg and both baselines (off: set up, warm up, time, print)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32)')
     args = ap.parse_args()
     if args.frames == 0:
         args.frames = 64 if args.config == 4 else 16
@@ -338,17 +351,36 @@ def stack_clips(group):
 
 
 def timed_clips(run_clip, batches, ddim_steps, n_steps, barrier, marks=None):
-    """EXACTLY n_steps steps (one step = one batch of clips through inversion + sampling) between two barriers."""
+    """EXACTLY n_steps steps (one step = one batch of clips through inversion + sampling) between two barriers.
+    -> (seconds, what the last step returned)"""
     barrier()
     t0 = time.perf_counter()
+    last = None
     for i in range(n_steps):
         if marks is not None:
             marks.append(_event())                   # clip start | (inside the clip) end of the inversion | clip end
-        run_clip(batches[i % len(batches)], ddim_steps, marks)
+        last = run_clip(batches[i % len(batches)], ddim_steps, marks)
         if marks is not None:
             marks.append(_event())
     barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """name -> tensor, written as directory/<name>.npy in float32.  An array beyond its share of DUMP_LIMIT_BYTES is
+    replaced by a fixed, seeded sample of its flattened elements (in index order), the same from run to run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, f'{name}.npy'), a.numpy())
 
 
 def workload_string(args, cps, lh, lw, swap=False, longclip=False):
@@ -436,6 +468,7 @@ def main():
             if m is not None:
                 m.append(_event())
             time.sleep(0.01)
+            return data['latents']                        # stands in for the denoised latents (--dump-outputs plumbing)
 
     def barrier():
         if distributed:
@@ -450,12 +483,17 @@ def main():
     if shard is not None:
         shard.bytes_gathered = 0
     ops.FlopCounter.reset(True)
-    prof = args.prof_samples > 0 and device.type == 'cuda'
+    prof = args.full and args.prof_samples > 0 and device.type == 'cuda'
     if prof:
         ops.prof_enable(True, args.prof_samples, stride=args.prof_stride)
     from videoswap_amd.telemetry import BoardPower
-    with BoardPower(local_rank if device.type == 'cuda' else -1) as bpw:      # host thread reading sysfs: nothing on the stream
-        elapsed = timed_clips(run_clip, batches, args.ddim_steps, args.steps, barrier, marks)
+    # host thread reading sysfs: nothing on the stream
+    bpw = BoardPower(local_rank if device.type == 'cuda' else -1) if args.full else None
+    with bpw if bpw is not None else contextlib.nullcontext():
+        elapsed, last = timed_clips(run_clip, batches, args.ddim_steps, args.steps, barrier, marks)
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, {'videos' if world == 1 else f'videos_rank{rank}': last})
+    del last
     # device time of the two halves of every clip (events on the launch stream; nothing was synchronised in between)
     inv_s = sum(marks[3 * i].elapsed_time(marks[3 * i + 1]) for i in range(args.steps)) * 1e-3
     smp_s = sum(marks[3 * i + 1].elapsed_time(marks[3 * i + 2]) for i in range(args.steps)) * 1e-3
@@ -508,7 +546,7 @@ def main():
                      'loop_mfma_frac': round(total_flop / elapsed / 1e12 / (MFMA_PEAK_TFLOPS * world), 4),
                      'ceiling_R1e_at_100pct_mfma': 15.1},
     }
-    if bpw.summary() is not None:           # rank 0's board over the timed region (MI355X: 1 400 W cap)
+    if bpw is not None and bpw.summary() is not None:     # rank 0's board over the timed region (MI355X: 1 400 W cap)
         out['readings']['board_power'] = bpw.summary()
         out['readings']['board_power']['joules_per_frame'] = round(bpw.summary()['mean_W'] * elapsed / max(frames_total / world, 1), 1)
     if distributed and world == 1:
@@ -534,7 +572,7 @@ def main():
         out['readings']['gemm_tflops_vs_power_managed_peak'] = note
         out['roofline'] = rl
     tcl = args.throughput_clips
-    if (rank == 0 and world == 1 and args.config == 2 and not args.no_extra_reading and not distributed and not stub
+    if (args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_extra_reading and not distributed and not stub
             and device.type == 'cuda' and tcl > 1 and tcl != cps and args.throughput_steps > 0):
         # SECOND LEG, never `value`: `tcl` independent configs[1] clips denoised together (UNet batch tcl in the inversion, 2 tcl
         # under CFG), fresh synthetic clips, one warm-up step + throughput_steps timed steps between barriers, its own sampled
@@ -549,7 +587,7 @@ def main():
             if prof:
                 ops.prof_enable(True, args.prof_samples, stride=args.prof_stride)
             with BoardPower(local_rank) as bpw2:
-                t2 = timed_clips(run_clip, tb, args.ddim_steps, nb, barrier)
+                t2, _ = timed_clips(run_clip, tb, args.ddim_steps, nb, barrier)
             roof2 = ops.prof_collect_roofline(MFMA_PEAK_TFLOPS * 1e12, HBM_COPY_TBPS * 1e12) if prof else dict(n=0, ms=0.0)
             if prof:
                 ops.prof_enable(False, 0)
@@ -567,7 +605,7 @@ def main():
             del extra, tb
         except Exception as e:  # the second leg must never take the headline down with it
             out['throughput_mode'] = {'clips_per_step': tcl, 'value': None, 'note': f'failed: {e!r}'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and device.type == 'cuda':
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and device.type == 'cuda':
         try:
             evals_per_s, threads, sample = cpu_baseline(args.cpu_frames, (lh, lw))
             out['cpu_baseline'] = {'value': round(evals_per_s / (3 * args.ddim_steps), 6), 'unit': 'frames/s',

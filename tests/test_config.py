@@ -15,7 +15,7 @@ import torch
 
 from util import DEV, GOLDEN, ROOT
 
-YML = '/root/reference/options/test_videoswap/animal/2001_catheadturn_T05_Iter100/2001_catheadturn_T05_Iter100.yml'
+YML = os.path.join(GOLDEN, '2001_catheadturn_T05_Iter100.yml')      # the reference's option file (settings only), as shipped
 OVERRIDES = {'datasets.num_frames': 4, 'val.editing_config.num_inference_steps': 2, 'mixed_precision': 'no',
              'val.save_type': 'frame_gif'}
 
@@ -39,10 +39,9 @@ def test_yaml_loader_reads_the_reference_option_file():
     assert gold['val']['editing_config']['editing_prompts']['kitten_to_dogA']['lora_path'].endswith('---0.7')
     assert gold['train']['optimizer']['lr'] == 5e-4 and gold['val']['editing_config']['use_blend'] is True
     assert gold['val']['editing_config']['editing_prompts']['kitten_to_catA']['tap_path'] is None
-    if os.path.isfile(YML):
-        assert load_options(YML) == gold
-        cfg = OmegaConf.load(YML)
-        assert cfg.models.unet.type == 'AnimateDiffUNet3DModel' and cfg.datasets.video_transform[0].size == 512
+    assert load_options(YML) == gold
+    cfg = OmegaConf.load(YML)
+    assert cfg.models.unet.type == 'AnimateDiffUNet3DModel' and cfg.datasets.video_transform[0].size == 512
     node = OmegaConf.create({'a': {'b': 3}, 'c': '${a.b}', 'd': 'x${a.b}y'})
     assert OmegaConf.to_container(node, resolve=True) == {'a': {'b': 3}, 'c': 3, 'd': 'x3y'}
 

@@ -105,10 +105,11 @@ def reference_trace():
 
 
 def test_controllers_match_reference_verbatim():
+    """Against the reference's controllers when the reference tree is present; else against the trace they produced
+    when tests/golden/p2p_trace.pt was recorded (`python tests/test_control.py`)."""
     from oracle import ref_import
-    if not ref_import.available():
-        pytest.skip('/root/reference is not present on this machine')
-    ref, prod = reference_trace(), product_trace()
+    ref = reference_trace() if ref_import.available() else load_golden('p2p_trace.pt')
+    prod = product_trace()
     assert len(ref) == len(prod)
     changed = 0
     for i, (a, b) in enumerate(zip(prod, ref)):

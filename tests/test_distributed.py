@@ -438,3 +438,33 @@ def test_bench_single_process_metric_arithmetic(cps, tmp_path):
     assert f'inversion (B={n})' in out['config']['workload'] and f'sampling (B={2 * n})' in out['config']['workload']
     assert abs(out['value'] - n * 3 * 16 / (out['ms_per_step'] * 3 / 1e3)) <= 0.02 * out['value']
     assert out['unit'] == 'frames/s' and out['dtype'] == 'f16' and out['data'] == 'synthetic' and out['scaling'] == 'weak'
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned (here the stub's stand-in: that step's input latents)
+    as float32 .npy, identical from run to run with the same arguments; `--full` runs to its one JSON line as well."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    from util import ROOT
+    env = dict(os.environ, VSX_BENCH_STUB_CLIP='1', CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES='', OMP_NUM_THREADS='2')
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'VSX_FORCE_DISTRIBUTED'):
+        env.pop(k, None)
+    dumps = []
+    for i, extra in enumerate(([], ['--full'])):
+        d = tmp_path / f'dump{i}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs', str(d)] + extra
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['ms_per_step'] >= 10.0
+        assert sorted(os.listdir(d)) == ['videos.npy']
+        dumps.append(np.load(d / 'videos.npy'))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1, 4, 16, 64, 64)
+    from videoswap_amd.synthetic import synthetic_clip
+    last = synthetic_clip(seed=2, frames=16, height=64, width=64, device='cpu')['latents']      # step 3 of 3: the third clip
+    assert np.array_equal(dumps[0], last.float().numpy()) and np.array_equal(dumps[0], dumps[1])

@@ -10,7 +10,7 @@ import random
 import pytest
 import torch
 
-from util import DEV, cosine, oracle_unet, product_unet_from, rel_l2
+from util import DEV, GOLDEN, cosine, load_golden, oracle_unet, product_unet_from, rel_l2
 
 NEEDS_BWD = [pytest.mark.device]
 TUNE = {'min_timestep': 0.5, 'drop_rate': 0.3, 'loss_type': 'local'}
@@ -24,27 +24,43 @@ def synthetic_batch(frames=2, hw=16, points=6, seed=3):
             'point_embedding': torch.randn(1, points, 1280, generator=g)}
 
 
-def test_oracle_adapter_training_branch_equals_reference_verbatim():
-    from oracle import adapter, ref_import
-    if not ref_import.available():
-        pytest.skip('/root/reference is not present')
+TRAIN_CHANS = [64, 128, 256, 256]
+
+
+def reference_training_branch_case():
+    """The reference's SparsePointAdapter, imported verbatim, in its training branch (dropped points, loss mask) on seeded
+    weights and the synthetic batch, python RNG seeded before every call."""
+    from oracle import adapter, ref_import, unet3d
     ref_import.load_reference_models()
     ref_import._load('videoswap.utils.registry', 'videoswap/utils/registry.py')
     ra = ref_import._load('videoswap.models.adapter_model', 'videoswap/models/adapter_model.py')
-    chans = [64, 128, 256, 256]
-    o = adapter.SparsePointAdapter(1280, chans).train()
-    r = ra.SparsePointAdapter(embedding_channels=1280, channels=chans).train()
-    r.load_state_dict(o.state_dict(), strict=True)
+    r = ra.SparsePointAdapter(embedding_channels=1280, channels=TRAIN_CHANS).train()
+    r.load_state_dict(unet3d.synth_weights_(adapter.SparsePointAdapter(1280, TRAIN_CHANS), seed=8).state_dict(), strict=True)
+    batch = synthetic_batch()
+    out = {}
+    for loss_type in ('local', 'global'):
+        random.seed(11)
+        sr, mr = r(batch['pred_tracks'], batch['img_size'], point_embedding=batch['point_embedding'], drop_rate=0.4,
+                   loss_type=loss_type)
+        out[loss_type] = ([t.detach().clone() for t in sr], mr.clone())
+    return out
+
+
+def test_oracle_adapter_training_branch_equals_reference_verbatim():
+    """Against the reference's code when the reference tree is present; else against what it returned when
+    tests/golden/adapter_train_verbatim.pt was recorded (`python tests/test_training.py`)."""
+    from oracle import adapter, ref_import, unet3d
+    ref = reference_training_branch_case() if ref_import.available() else load_golden('adapter_train_verbatim.pt')
+    o = unet3d.synth_weights_(adapter.SparsePointAdapter(1280, TRAIN_CHANS), seed=8).train()
     batch = synthetic_batch()
     for loss_type in ('local', 'global'):
         random.seed(11)
         so, mo = o(batch['pred_tracks'], batch['img_size'], batch['point_embedding'], drop_rate=0.4, loss_type=loss_type)
-        random.seed(11)
-        sr, mr = r(batch['pred_tracks'], batch['img_size'], point_embedding=batch['point_embedding'], drop_rate=0.4,
-                   loss_type=loss_type)
+        sr, mr = ref[loss_type]
         assert torch.equal(mo, mr) and (loss_type == 'global' or 0 < float(mo.mean()) < 1)
-        for a, b in zip(so, sr):
-            assert torch.equal(a, b)
+        assert len(so) == len(sr)
+        for a, b in zip(so, sr):        # a recorded copy may come from another CPU's kernels: float tolerance
+            assert torch.equal(a, b) if ref_import.available() else torch.allclose(a, b, rtol=1e-5, atol=1e-6)
 
 
 def _models():
@@ -233,3 +249,10 @@ def test_noise_schedule_and_lr_schedules_closed_forms():
     assert lin[:3] == [0.0, 0.5, 1.0] and abs(lin[6] - 0.5) < 1e-9 and lin[10] == 0.0
     cos = lrs('cosine', 0, 8, 9)
     assert abs(cos[4] - 0.5) < 1e-9 and abs(cos[2] - 0.5 * (1 + math.cos(math.pi * 0.25))) < 1e-9 and cos[8] < 1e-9
+
+
+if __name__ == '__main__':   # record the reference's outputs (needs the reference tree)
+    import sys
+    sys.dont_write_bytecode = True
+    torch.save(reference_training_branch_case(), os.path.join(GOLDEN, 'adapter_train_verbatim.pt'))
+    print('wrote adapter_train_verbatim.pt')

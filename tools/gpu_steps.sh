@@ -12,8 +12,8 @@
 #   hip:<name>     hipcc tools/ubench/<name>.hip && run it
 #   kernels        pytest tests/test_kernels_gpu.py
 #   pytest         the whole -m gpu suite
-#   bench          python bench.py             (default line, both baseline legs)
-#   benchq         python bench.py --no-cpu-baseline --steps 2 --warmup 1
+#   bench          python bench.py --full      (roofline, throughput leg, both baseline legs)
+#   benchq         python bench.py --full --no-cpu-baseline --steps 2 --warmup 1
 #   benchcfg3      python bench.py --config 3 ...   (configs[2]: the full swap path)
 #   bench448       python bench.py --latent-h 56 --latent-w 96 ...   (448x768 frames: 26 of the 30 reference option files)
 #   bench2         python bench.py --clips-per-step 2 ...   (two clips denoised together)
@@ -69,22 +69,22 @@ for STEP in "$@"; do
     pytest)
       ( time timeout 1700 python -m pytest tests -m gpu -x -q --durations=12 -rf ) > $O/${TAG}_pytest.txt 2>&1; show pytest 24 ;;
     bench)
-      timeout 500 python bench.py > $O/${TAG}_bench.txt 2>&1; show bench 1 3500 ;;
+      timeout 500 python bench.py --full > $O/${TAG}_bench.txt 2>&1; show bench 1 3500 ;;
     benchq)
-      timeout 400 python bench.py --no-cpu-baseline --steps 2 --warmup 1 > $O/${TAG}_benchq.txt 2>&1; show benchq 1 3500 ;;
+      timeout 400 python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 > $O/${TAG}_benchq.txt 2>&1; show benchq 1 3500 ;;
     benchcfg3)
-      timeout 400 python bench.py --config 3 --steps 1 --warmup 1 --no-cpu-baseline > $O/${TAG}_benchcfg3.txt 2>&1; show benchcfg3 1 600 ;;
+      timeout 400 python bench.py --full --config 3 --steps 1 --warmup 1 --no-cpu-baseline > $O/${TAG}_benchcfg3.txt 2>&1; show benchcfg3 1 600 ;;
     bench448)
-      timeout 400 python bench.py --latent-h 56 --latent-w 96 --steps 1 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench448.txt 2>&1; show bench448 1 600 ;;
+      timeout 400 python bench.py --full --latent-h 56 --latent-w 96 --steps 1 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench448.txt 2>&1; show bench448 1 600 ;;
     bench2)
-      timeout 400 python bench.py --clips-per-step 2 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-reading > $O/${TAG}_bench2.txt 2>&1; show bench2 1 1500 ;;
+      timeout 400 python bench.py --full --clips-per-step 2 --steps 2 --warmup 1 --no-cpu-baseline --no-extra-reading > $O/${TAG}_bench2.txt 2>&1; show bench2 1 1500 ;;
     benchenv:*)       # benchenv:NAME=VALUE:clips — one quick bench line under an environment switch (in-situ A/B of an option)
       A=${STEP#benchenv:}; E=${A%%:*}; N=${A##*:}
       env $E timeout 600 python bench.py --clips-per-step $N --steps 2 --warmup 1 --no-cpu-baseline --no-extra-reading > $O/${TAG}_benchenv.txt 2>&1
       tail -n 1 $O/${TAG}_benchenv.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['readings']; print('$E clips/step $N:', d['value'], 'fps; inv', r['inversion_s_per_clip'], 'smp', r['sampling_s_per_clip'])" ;;
     benchn:*)
       N=${STEP#benchn:}
-      timeout 600 python bench.py --clips-per-step $N --steps 2 --warmup 1 --no-cpu-baseline --no-extra-reading > $O/${TAG}_benchn$N.txt 2>&1
+      timeout 600 python bench.py --full --clips-per-step $N --steps 2 --warmup 1 --no-cpu-baseline --no-extra-reading > $O/${TAG}_benchn$N.txt 2>&1
       tail -n 1 $O/${TAG}_benchn$N.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['readings']; print('clips/step $N:', d['value'], 'fps; ms_per_step', d['ms_per_step'], 'inv', r['inversion_s_per_clip'], 'smp', r['sampling_s_per_clip'], 'gemm frac', d['roofline']['frac'], 'attainable', d['roofline']['frac_of_attainable'], 'byte-bound share', d['roofline']['byte_bound_time_share'])" ;;
     smoke)
       timeout 400 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${TAG}_smoke.txt 2>&1; show smoke 3 ;;
@@ -115,9 +115,9 @@ for STEP in "$@"; do
       timeout 300 python tools/train_bench.py --steps 3 > $O/${TAG}_train.txt 2>&1; show train 4 ;;
     dist1)
       VSX_FORCE_DISTRIBUTED=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 \
-        bench.py --gpus 1 --steps 1 --warmup 0 --ddim-steps 4 --no-cpu-baseline > $O/${TAG}_dist1_clip.txt 2>&1; show dist1_clip 2 3000
+        bench.py --full --gpus 1 --steps 1 --warmup 0 --ddim-steps 4 --no-cpu-baseline > $O/${TAG}_dist1_clip.txt 2>&1; show dist1_clip 2 3000
       VSX_FORCE_DISTRIBUTED=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 \
-        bench.py --gpus 1 --config 4 --frames 32 --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline > $O/${TAG}_dist1_long.txt 2>&1; show dist1_long 2 3000 ;;
+        bench.py --full --gpus 1 --config 4 --frames 32 --steps 1 --warmup 0 --ddim-steps 2 --no-cpu-baseline > $O/${TAG}_dist1_long.txt 2>&1; show dist1_long 2 3000 ;;
     *) echo "unknown step $STEP" ;;
   esac
   el $STEP
