@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 10
+#define VSX_ABI_VERSION 11
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -379,6 +379,31 @@ int vsx_softmax_bwd(const void* P, void* dP, int64_t nrows, int64_t ncols, int64
 int vsx_sum_pool2x2(const void* x, void* y, int64_t n, int64_t h, int64_t w, int64_t c, vsx_stream_t stream);
 int vsx_adapter_gather(const float* tracks, const int32_t* selected, const void* dmap, void* dfeat, int64_t F,
                        int64_t P, int64_t C, int64_t h, int64_t w, float rate, float out_scale, vsx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K12 (ABI 11): DIFT semantic-point embeddings (extract_semantic_point.py:125-205, dift_util.py:230-267).
+ * `feat` is the UNet feature tap of AnimateDiffUNet3DModel.forward_features: fp16 [N, E, h, w, C] channels-last
+ * (N frames, E ensemble members), C a multiple of 8.  The reference averages the E maps, upsamples the mean to the
+ * image size (H, W) with nn.Upsample(mode='bilinear', align_corners=False) and reads / compares pixels of that fp32
+ * map; these entry points compute the same numbers without building it (csrc/dift.hip).
+ *   vsx_dift_sample_points: coords int32 [N, P, 2] = (x, y) pixels of the output image, x < 0 = skip the point.
+ *       vec fp32 [N, P, C] = the upsampled ensemble mean at (y, x) (zeros for a skipped point); optional
+ *       cos fp32 [N, P] = <vec, q> / max(|vec| |q|, 1e-8) against query fp32 [P, C] (query_per_frame 0) or
+ *       [N, P, C] (query_per_frame 1); 0 for a skipped point.  query may be NULL when cos is NULL.
+ *   vsx_dift_cosine_map: Q query vectors fp32 [Q, C] (or [N, Q, C]); optional cos_map fp32 [N, Q, H, W] = the
+ *       cosine of every pixel of the upsampled mean map with each query (NULL: not written); argmax_yx int32
+ *       [N, Q, 2] = (y, x) of the largest cosine, the first in row-major order among equal values
+ *       (np.unravel_index(argmax)); argmax_val fp32 [N, Q] its value.  workspace: caller-allocated,
+ *       vsx_dift_cosine_map_workspace(N, h, w, C, Q) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int vsx_dift_sample_points(const void* feat, int64_t N, int64_t E, int64_t h, int64_t w, int64_t C, int64_t H,
+                           int64_t W, const int32_t* coords, int64_t P, const float* query, int64_t query_per_frame,
+                           float* vec, float* cos_out, vsx_stream_t stream);
+int64_t vsx_dift_cosine_map_workspace(int64_t N, int64_t h, int64_t w, int64_t C, int64_t Q);
+int vsx_dift_cosine_map(const void* feat, int64_t N, int64_t E, int64_t h, int64_t w, int64_t C, int64_t H, int64_t W,
+                        const float* query, int64_t Q, int64_t query_per_frame, void* workspace,
+                        int64_t workspace_bytes, float* cos_map, int32_t* argmax_yx, float* argmax_val,
+                        vsx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 10
+VSX_ABI_VERSION = 11
 
 
 class VsxError(RuntimeError):
@@ -115,6 +115,12 @@ PROTOTYPES = {
                                    c_float, c_float, c_void_p]),
     'vsx_alltoall_f16': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64),
                                  c_void_p]),
+    # DIFT semantic-point embeddings (csrc/dift.hip)
+    'vsx_dift_sample_points': (c_int, [c_void_p] + [c_int64] * 7 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                                                       c_void_p, c_void_p]),
+    'vsx_dift_cosine_map_workspace': (c_int64, [c_int64] * 5),
+    'vsx_dift_cosine_map': (c_int, [c_void_p] + [c_int64] * 7 + [c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

@@ -190,6 +190,16 @@ class DDIMScheduler(_DDIMBase):
         final = 1.0 if self.config.set_alpha_to_one else float(self.alphas_cumprod[0])
         return float(self.alphas_cumprod[t]), (float(self.alphas_cumprod[prev]) if prev >= 0 else final)
 
+    def add_noise(self, original_samples, noise, timesteps):
+        """q(x_t | x_0) = sqrt(abar_t) x_0 + sqrt(1 - abar_t) eps, the formula of DDPMScheduler.add_noise (the DIFT
+        featurizer noises its latents with the sampling scheduler, dift_util.py:176)."""
+        if not torch.is_tensor(timesteps):
+            timesteps = torch.tensor(timesteps)
+        a = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)[
+            timesteps.to(original_samples.device).long()]
+        shape = (-1,) + (1,) * (original_samples.dim() - 1) if a.dim() else ()
+        return (a ** 0.5).reshape(shape) * original_samples + ((1 - a) ** 0.5).reshape(shape) * noise
+
 
 class DDIMInverseScheduler(_DDIMBase):
     """Inversion direction, diffusers 0.18-0.19 variant: timesteps -19, 1, 21, ..., 961; each step moves

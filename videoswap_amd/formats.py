@@ -63,6 +63,20 @@ def load_tap(path):
     return tap
 
 
+def load_tracks(path):
+    """The INPUT of point extraction (videoswap_amd.extract_points): a TAP-like dict with `pred_tracks [F, P, 2]` and
+    `point_name2id`; any `point_embedding` in it is ignored (dropped).  `load_tap` keeps requiring all three keys."""
+    tap = _load(path)
+    if not isinstance(tap, dict) or any(k not in tap for k in ('pred_tracks', 'point_name2id')):
+        raise FormatError(f'{path}: a track file is a dict with keys pred_tracks, point_name2id')
+    tracks, names = tap['pred_tracks'], tap['point_name2id']
+    if not torch.is_tensor(tracks) or tracks.dim() != 3 or tracks.shape[-1] != 2:
+        raise FormatError(f'{path}: pred_tracks must be a [frames, points, 2] tensor')
+    if not all(0 <= int(i) < tracks.shape[1] for i in names.values()):
+        raise FormatError(f'{path}: point_name2id refers to points outside [0, {tracks.shape[1]})')
+    return {'pred_tracks': tracks, 'point_name2id': dict(names)}
+
+
 def save_tap(path, pred_tracks, point_embedding, point_name2id):
     os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
     torch.save({'pred_tracks': pred_tracks, 'point_embedding': point_embedding,

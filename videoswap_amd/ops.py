@@ -726,6 +726,61 @@ def adapter_scatter(tracks, selected, feat, h, w, rate, out_scale=1.0):
     return out
 
 
+def _dift_feat(feat):
+    _chk(feat, 'feat')
+    if feat.dim() != 5 or feat.shape[-1] % 8:
+        raise _lib.VsxError(f'dift: feat must be [N, E, h, w, C] with C % 8 == 0, got {tuple(feat.shape)}')
+    return feat.shape
+
+
+def _dift_query(query, N, lead, C, name='query'):
+    """[lead, C] (shared by all frames) or [N, lead, C] fp32 -> per-frame flag"""
+    _chk(query, name, torch.float32)
+    if query.shape[-1] != C or tuple(query.shape[:-1]) not in ((lead,), (N, lead)):
+        raise _lib.VsxError(f'dift: {name} must be [{lead}, {C}] or [{N}, {lead}, {C}], got {tuple(query.shape)}')
+    return int(query.dim() == 3)
+
+
+def dift_sample_points(feat, size, coords, query=None, want_cos=False):
+    """feat fp16 [N, E, h, w, C] (the UNet tap, ensemble members of a frame adjacent); size (H, W) of the image;
+    coords int32 [N, P, 2] = pixel (x, y), x < 0 = skip -> (vec fp32 [N, P, C], cos fp32 [N, P] or None).  vec is the
+    bilinear (align_corners=False) upsampling of the ensemble mean to (H, W), read at (y, x)."""
+    N, E, h, w, C = _dift_feat(feat)
+    _chk(coords, 'coords', torch.int32)
+    if coords.dim() != 3 or coords.shape[0] != N or coords.shape[2] != 2:
+        raise _lib.VsxError(f'dift_sample_points: coords must be [{N}, P, 2], got {tuple(coords.shape)}')
+    P = coords.shape[1]
+    H, W = (int(s) for s in size)
+    per_frame = 0
+    if query is not None:
+        per_frame = _dift_query(query, N, P, C)
+    elif want_cos:
+        raise _lib.VsxError('dift_sample_points: cos needs query vectors')
+    vec = torch.empty(N, P, C, dtype=torch.float32, device=feat.device)
+    cos = torch.empty(N, P, dtype=torch.float32, device=feat.device) if want_cos else None
+    check(_lib.load().vsx_dift_sample_points(_p(feat), N, E, h, w, C, H, W, _p(coords), P, _p(query), per_frame,
+                                             _p(vec), _p(cos), _stream()), 'vsx_dift_sample_points')
+    return vec, cos
+
+
+def dift_cosine_map(feat, size, query, want_map=True):
+    """feat fp16 [N, E, h, w, C]; query fp32 [Q, C] or [N, Q, C] -> (cos map fp32 [N, Q, H, W] or None,
+    argmax int32 [N, Q, 2] = (y, x) (first in row-major order among equal values), max fp32 [N, Q]).  Never builds the
+    upsampled [C, H, W] map (csrc/dift.hip)."""
+    N, E, h, w, C = _dift_feat(feat)
+    Q = query.shape[-2]
+    per_frame = _dift_query(query, N, Q, C)
+    H, W = (int(s) for s in size)
+    lib = _lib.load()
+    ws = torch.empty(lib.vsx_dift_cosine_map_workspace(N, h, w, C, Q), dtype=torch.uint8, device=feat.device)
+    cmap = torch.empty(N, Q, H, W, dtype=torch.float32, device=feat.device) if want_map else None
+    yx = torch.empty(N, Q, 2, dtype=torch.int32, device=feat.device)
+    val = torch.empty(N, Q, dtype=torch.float32, device=feat.device)
+    check(lib.vsx_dift_cosine_map(_p(feat), N, E, h, w, C, H, W, _p(query), Q, per_frame, _p(ws), ws.numel(), _p(cmap),
+                                  _p(yx), _p(val), _stream()), 'vsx_dift_cosine_map')
+    return cmap, yx, val
+
+
 _options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0'))}
 
 
@@ -947,7 +1002,7 @@ _ACTIVATIONS = {
 }
 _PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
-          'attention_bwd', 'attention_bwd_supported')
+          'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map')
 
 
 def _publish(name):

@@ -711,6 +711,50 @@ class AnimateDiffUNet3DModel(ModelMixin, ConfigMixin):
         x = self.conv_out(x)
         return ops.unpack_latents(x, B, self.config.out_channels)
 
+    @torch.no_grad()
+    def forward_features(self, sample, timestep, encoder_hidden_states, up_ft_indices):
+        """The DIFT feature tap (MyUNet2DConditionModel.forward, dift_util.py:14-162): conv_in, the down blocks, the mid
+        block and the up blocks 0 ... max(up_ft_indices), each with its upsampler; nothing after (no later up block, no
+        conv_norm_out / conv_out).  -> {i: output of up block i}, channels-last fp16 [B*F, h, w, C].
+
+        Built for the 2-D SD UNet (`use_motion_module=False`) called with F = 1 and B = images: the 5-D GroupNorm over one
+        frame is then the 2-D one.  `encoder_hidden_states` may be ONE prompt [1, 77, D]: the native cross-attention reads
+        its K / V for every image (`kv_div` = B*F, attention.py), so the text is never repeated.  Eager only: no HIP graph,
+        no adapter residuals, no shared CFG prefix, no frame sharding."""
+        idx = sorted({int(i) for i in up_ft_indices})
+        if not idx or idx[0] < 0 or idx[-1] >= len(self.up_blocks):
+            raise ValueError(f'up_ft_indices must lie in [0, {len(self.up_blocks) - 1}], got {list(up_ft_indices)}')
+        if sample.dim() != 5:
+            raise ValueError(f'expected [B, C, F, H, W], got {tuple(sample.shape)}')
+        if self._frame_shard is not None:
+            raise NotImplementedError('forward_features: not in the frame-sharded mode')
+        B, _, F, H, W = sample.shape
+        up = 2 ** self.num_upsamplers
+        if H % up or W % up:
+            raise NotImplementedError(f'latent sides must be multiples of {up} (got {H}x{W})')
+        timesteps = timestep
+        if not torch.is_tensor(timesteps):
+            timesteps = torch.tensor([timesteps], dtype=torch.float64 if isinstance(timestep, float) else torch.int64)
+        elif timesteps.dim() == 0:
+            timesteps = timesteps[None]
+        silu_emb = self._silu_time_embedding(timesteps, B, sample.device)
+        geo = Geometry(B, F)
+
+        x = self.conv_in(ops.pack_latents(sample.contiguous(), 8))
+        skips = (x,)
+        for blk in self.down_blocks:
+            x, outs = blk(x, silu_emb, geo, encoder_hidden_states=encoder_hidden_states)
+            skips += outs
+        x = self.mid_block(x, silu_emb, geo, encoder_hidden_states=encoder_hidden_states)
+        feats = {}
+        for i, blk in enumerate(self.up_blocks[:idx[-1] + 1]):
+            n = len(blk.resnets)
+            res, skips = skips[-n:], skips[:-n]
+            x = blk(x, res, silu_emb, geo, encoder_hidden_states=encoder_hidden_states)
+            if i in idx:
+                feats[i] = x
+        return feats
+
     # ---------------------------------------------------------------------------------------------
     def enable_hip_graphs(self, enabled=True, eager_every=0):
         """Replay the forward as a captured HIP graph (one per input signature) instead of ~700 eager launches: the
