@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 11
+#define VSX_ABI_VERSION 12
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -404,6 +404,29 @@ int vsx_dift_cosine_map(const void* feat, int64_t N, int64_t E, int64_t h, int64
                         const float* query, int64_t Q, int64_t query_per_frame, void* workspace,
                         int64_t workspace_bytes, float* cos_map, int32_t* argmax_yx, float* argmax_val,
                         vsx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K13 (ABI 12): fused coordinate MLP of the layered neural atlas = IMLP_Hash.forward with mlp_type 'origin'
+ * (videoswap/atlas/implicit_neural_networks.py:164-195; the three networks propagate_point_displacement.py evaluates).
+ * ALL tensors are fp32 and the arithmetic is fp32 throughout (fp32-input MFMA: one rounding per product, fp32 sums).
+ *   x [N, input_dim] (input_dim 2 or 3) -> out [N, output_dim] (output_dim 1 to 3), both dense row-major, any N >= 0.
+ *   pe_type 0 = 'none' (the coordinates feed layer 0), 1 = 'encoding' (positionalEncoding_vec with pe_dim frequencies
+ *   2^j pi: per frequency the sines of all inputs, then the cosines; 2 * input_dim * pe_dim <= 64 columns),
+ *   2 = 'hash_encoding' -> VSX_E_UNSUPPORTED.  mlp_type 0 = 'origin', 1 = 'tcnn' -> VSX_E_UNSUPPORTED.
+ *   mlp_layers 2 to 8 (the output layer included), hidden_dim a multiple of 32 up to 256, ReLU before every layer but
+ *   the first, bias on every layer, tanh on the output when use_tanh != 0.  skip_mask: bit i set = layer i reads
+ *   cat(hidden activations, encoded input) (skip_layers; i in 1 .. mlp_layers - 1).
+ *   packed: every layer's weight and bias in the layout the kernel streams, 16-byte aligned, packed_floats in all.
+ *   Layer l has K = (l > 0 ? hidden_dim : 0) + (l == 0 or skip ? E8 : 0) input columns, E8 = the encoded width rounded
+ *   up to a multiple of 8, and F = hidden_dim output features (the last layer: 32); the nn.Linear weight [out, in] is
+ *   zero-padded to [F, K] (the encoded columns sit after the hidden ones, as torch.cat((x, input), 1) puts them).
+ *   Layers follow each other; a layer is F * K floats of weight, then F floats of bias.  The weight is stored as
+ *   [F / 32][K / 8][2][32][4]: element [t][b][h][i][s] = W[32 t + i][8 b + 4 h + s] (the float4 that lane 32 h + i of
+ *   a wave feeds to four consecutive v_mfma_f32_32x32x2_f32).
+ * ------------------------------------------------------------------------------------------ */
+int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
+                      int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask,
+                      int64_t use_tanh, const float* packed, int64_t packed_floats, float* out, vsx_stream_t stream);
 
 #ifdef __cplusplus
 }

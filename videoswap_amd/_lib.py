@@ -13,7 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 11
+VSX_ABI_VERSION = 12
+VSX_E_UNSUPPORTED = -2
 
 
 class VsxError(RuntimeError):
@@ -121,6 +122,8 @@ PROTOTYPES = {
     'vsx_dift_cosine_map_workspace': (c_int64, [c_int64] * 5),
     'vsx_dift_cosine_map': (c_int, [c_void_p] + [c_int64] * 7 + [c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    # fused coordinate MLP of the neural atlas (csrc/atlas.hip)
+    'vsx_coord_mlp_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

@@ -1,0 +1,220 @@
+"""Layered-neural-atlas point propagation: the host side of propagate_point_displacement.py (reference :20-126).
+
+A drag of a few semantic points on one keyframe is carried to every frame through a TRAINED atlas: the keyframe point
+goes to the canonical (u, v) space with `FG_UV_Mapping`, comes back to every frame with `FG_UV_Mapping_Inverse`, and the
+displacement follows through two finite-difference Jacobians; `F_Alpha` decides in which frames the point is visible.
+The three networks are plain coordinate MLPs (`IMLP_Hash` with mlp_type 'origin'); each is evaluated by ONE launch of the
+fused kernel `ops.coord_mlp` (csrc/atlas.hip), and the propagation is batched over all dragged points and frames: three
+launches whatever the number of points P and frames T (the reference makes about ten tiny calls per point).  Per row the
+arithmetic is that of the reference's per-point calls.  Training an atlas (train_atlas.py, the hash-grid texture
+network `F_Atlas`, the losses) is out of scope.
+"""
+import json
+import os
+
+import torch
+import torch.nn as nn
+
+from . import ops
+
+DELTAX, DELTAY = 0.1, 0.05            # finite-difference steps of compute_Wm's callers, in normalised units
+MODEL_NAMES = ('FG_UV_Mapping', 'FG_UV_Mapping_Inverse', 'F_Alpha')
+
+
+def pack_coord_mlp(weights, biases, hidden_dim, enc_dim, skip_layers=()):
+    """nn.Linear weights [out, in] / biases of one network -> the fp32 buffer `ops.coord_mlp` streams (include/vsx.h K13):
+    per layer the weight zero-padded to [F, K] (F = hidden_dim, 32 for the last layer; K = hidden columns, then the encoded
+    columns padded to a multiple of 8) as [F / 32][K / 8][2][32][4] = W[32 t + i][8 b + 4 h + s], then F floats of bias."""
+    encp = (enc_dim + 7) // 8 * 8
+    last = len(weights) - 1
+    parts = []
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        w, b = w.detach().to(torch.float32), b.detach().to(torch.float32)
+        F = 32 if l == last else hidden_dim
+        kh = hidden_dim if l > 0 else 0
+        ke = encp if (l == 0 or l in skip_layers) else 0
+        if w.shape[1] != kh + (enc_dim if ke else 0) or w.shape[0] > F:
+            raise ValueError(f'layer {l}: weight {tuple(w.shape)} does not fit hidden_dim {hidden_dim} / {enc_dim} encoded columns')
+        full = torch.zeros(F, kh + ke, dtype=torch.float32, device=w.device)
+        full[:w.shape[0], :w.shape[1]] = w
+        parts.append(full.view(F // 32, 32, (kh + ke) // 8, 2, 4).permute(0, 2, 3, 1, 4).reshape(-1))
+        fb = torch.zeros(F, dtype=torch.float32, device=w.device)
+        fb[:b.shape[0]] = b
+        parts.append(fb)
+    return torch.cat(parts).contiguous()
+
+
+class CoordMLP(nn.Module):
+    """`IMLP_Hash` (videoswap/atlas/implicit_neural_networks.py:98-195): same constructor arguments, same state-dict keys
+    (`hidden.<i>.weight` / `hidden.<i>.bias`); `forward` is one launch of the fused fp32 kernel.  `pe_type:
+    hash_encoding` and `mlp_type: tcnn` (tinycudann) are not implemented."""
+
+    def __init__(self, input_dim, output_dim, hidden_dim=256, pe_type='none', pe_dim=10, mlp_type='origin', skip_layers=(),
+                 mlp_layers=8, use_tanh=True, fp16=False):
+        super().__init__()
+        if pe_type == 'hash_encoding':
+            raise NotImplementedError("CoordMLP: pe_type 'hash_encoding' (the tinycudann hash grid of F_Atlas) is not "
+                                      "implemented; point propagation does not use it")
+        if pe_type not in ('none', 'encoding'):
+            raise NotImplementedError(f'CoordMLP: pe_type {pe_type!r}')
+        if mlp_type != 'origin':
+            raise NotImplementedError(f"CoordMLP: mlp_type {mlp_type!r} is not implemented, only 'origin' (nn.Linear layers)")
+        self.input_dim, self.output_dim, self.hidden_dim = int(input_dim), int(output_dim), int(hidden_dim)
+        self.pe_type, self.pe_dim, self.mlp_type = pe_type, int(pe_dim), mlp_type
+        self.skip_layers, self.mlp_layers, self.use_tanh = [int(i) for i in skip_layers], int(mlp_layers), bool(use_tanh)
+        self.encoding_dimensions = 2 * self.input_dim * self.pe_dim if pe_type == 'encoding' else self.input_dim
+        self.hidden = nn.ModuleList()
+        for i in range(self.mlp_layers):
+            if i == 0:
+                k = self.encoding_dimensions
+            elif i in self.skip_layers:
+                k = self.hidden_dim + self.encoding_dimensions
+            else:
+                k = self.hidden_dim
+            self.hidden.append(nn.Linear(k, self.output_dim if i == self.mlp_layers - 1 else self.hidden_dim, bias=True))
+        self._packed = None               # (key, buffer): packed once, again only when a parameter changed or moved
+
+    def packed(self):
+        params = [q for lin in self.hidden for q in (lin.weight, lin.bias)]
+        key = tuple((q.data_ptr(), q._version, q.device) for q in params)
+        if self._packed is None or self._packed[0] != key:
+            self._packed = (key, pack_coord_mlp([lin.weight for lin in self.hidden], [lin.bias for lin in self.hidden],
+                                                self.hidden_dim, self.encoding_dimensions, self.skip_layers))
+        return self._packed[1]
+
+    def forward(self, x):
+        lead = x.shape[:-1]
+        x = x.reshape(-1, self.input_dim).to(torch.float32).contiguous()
+        y = ops.coord_mlp(x, self.packed(), self.input_dim, self.output_dim, self.hidden_dim, self.mlp_layers,
+                          pe_type=self.pe_type, pe_dim=self.pe_dim, mlp_type=self.mlp_type, skip_layers=self.skip_layers,
+                          use_tanh=self.use_tanh)
+        return y.reshape(*lead, self.output_dim)
+
+
+def load_atlas_config(path):
+    """The reference's atlas YAML (options/train_videoswap/*/*/*atlas*.yml) as a plain dict."""
+    from .config import load_options
+    return load_options(path)
+
+
+def load_atlas_models(atlas_config, checkpoint_path, device=None):
+    """init_atlas_model (propagate_point_displacement.py:59-74) -> (FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha).
+    `atlas_config`: the dict or the path of the YAML.  Every other entry of the checkpoint (BG_UV_Mapping, the hash-grid
+    F_Atlas, optimizer state) is ignored."""
+    from . import formats
+    if isinstance(atlas_config, (str, os.PathLike)):
+        atlas_config = load_atlas_config(atlas_config)
+    ckpt = formats._load(checkpoint_path)
+    models = []
+    for name in MODEL_NAMES:
+        if name not in atlas_config.get('models', {}):
+            raise formats.FormatError(f'atlas config: models.{name} is missing')
+        if not isinstance(ckpt, dict) or name not in ckpt:
+            raise formats.FormatError(f'{checkpoint_path}: no {name!r} state dict')
+        try:
+            m = CoordMLP(**atlas_config['models'][name])
+        except NotImplementedError as e:
+            raise NotImplementedError(f'models.{name}: {e}') from e
+        m.load_state_dict(ckpt[name])
+        models.append(m.to(device) if device is not None else m)
+    return tuple(models)
+
+
+def number_of_frames(atlas_config, num_frames=None):
+    """min(max_frames, number of frame files) as load_input_data counts (unwrap_utils.py:43-44), without reading a frame;
+    `num_frames` stands in for the file count."""
+    ds = atlas_config['datasets']
+    if num_frames is None:
+        path = ds.get('frame_path')
+        if not path or not os.path.isdir(path):
+            raise FileNotFoundError(f'datasets.frame_path {path!r} is not a directory: pass --num_frames')
+        num_frames = len(os.listdir(path))
+    return int(min(int(ds['max_frames']), int(num_frames)))
+
+
+def compute_Wm(xyt, func, deltax, deltay, return_base=False):
+    """[..., 3] -> [..., 2, C]: forward differences of `func` along x and y (reference :20-35).  The three stencil points
+    of every row go through `func` in ONE call; `return_base` also hands back func(xyt)."""
+    lead = xyt.shape[:-1]
+    pts = xyt.unsqueeze(0).repeat(3, *([1] * xyt.dim()))
+    pts[1, ..., 0] = xyt[..., 0] + deltax
+    pts[2, ..., 1] = xyt[..., 1] + deltay
+    uv = func(pts.reshape(-1, xyt.shape[-1])).reshape(3, *lead, -1)
+    Wm = torch.stack([(uv[1] - uv[0]) / deltax, (uv[2] - uv[0]) / deltay], dim=-2)
+    return (Wm, uv[0]) if return_base else Wm
+
+
+def propagate_point(source_xy, target_xy, t, number_of_frames, FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha,
+                    norm_Scoord_func, norm_Tcoord_func, device):
+    """All dragged points at once.  source_xy / target_xy: [P, 2] pixel (x, y) at keyframe t (float64 lists or tensors)
+    -> (warp_xy [P, T, 2] normalised, alpha [P, T]).  Three network calls: FG_UV_Mapping on [3 P] rows,
+    FG_UV_Mapping_Inverse on [3 P T] rows (the base point is the centre of the stencil), F_Alpha on [P T] rows."""
+    T = int(number_of_frames)
+    src = torch.as_tensor(source_xy, dtype=torch.float64).reshape(-1, 2)
+    tgt = torch.as_tensor(target_xy, dtype=torch.float64).reshape(-1, 2)
+    P = src.shape[0]
+    # the reference normalises in Python floats (float64) and rounds once to fp32
+    xyt = torch.cat([norm_Scoord_func(src), torch.full((P, 1), float(norm_Tcoord_func(t)), dtype=torch.float64)], 1)
+    xyt = xyt.to(torch.float32).to(device)
+    dx_dy = (norm_Scoord_func(tgt) - norm_Scoord_func(src)).to(torch.float32).to(device)           # [P, 2]
+
+    # stage 1: keyframe point -> canonical space, with its Jacobian
+    W_fwd, uv = compute_Wm(xyt, FG_UV_Mapping, DELTAX, DELTAY, return_base=True)                   # [P, 2, 2], [P, 2]
+    delta_uv = torch.bmm(dx_dy.unsqueeze(1), W_fwd)                                                # [P, 1, 2]
+
+    # stage 2: canonical point -> every frame: the base coordinate and the inverse Jacobian
+    frames = torch.arange(T, device=device).unsqueeze(-1)
+    tn = norm_Tcoord_func(frames).to(torch.float32)                                                # [T, 1]
+    uvt = torch.cat([uv.unsqueeze(1).expand(P, T, 2), tn.unsqueeze(0).expand(P, T, 1)], dim=-1)    # [P, T, 3]
+    W_inv, xyt_pred = compute_Wm(uvt, FG_UV_Mapping_Inverse, DELTAX, DELTAY, return_base=True)     # [P, T, 2, 3], [P, T, 3]
+    delta_xy = torch.matmul(delta_uv.unsqueeze(1), W_inv[..., :2]).squeeze(2)                      # [P, T, 2]
+    warp_xy = xyt_pred[..., :2] + delta_xy
+
+    # stage 3: visibility at the un-dragged location
+    alpha = 0.5 * (F_Alpha(xyt_pred.reshape(P * T, 3)).reshape(P, T) + 1.0)
+    return warp_xy, alpha
+
+
+def propagate_point_sequence(source_point_path, source_tap_path, target_point_path, FG_UV_Mapping, FG_UV_Mapping_Inverse,
+                             F_Alpha, larger_dim, number_of_frames, norm_Scoord_func=None, norm_Tcoord_func=None,
+                             device=None, return_details=False):
+    """propagate_point_sequence (reference :77-126) -> the TAP dict with the dragged tracks replaced.  JSON points are
+    [y, x].  A dragged point's whole track becomes [-1, -1]; frames with alpha > 0.5 get round((xy + 1) / 2 * larger_dim)
+    (torch.round: half to even).  Points the target file does not name keep their tracks; names only in the target file
+    are ignored; point_embedding / point_name2id pass through; rows past `number_of_frames` keep [-1, -1]."""
+    from . import formats
+    larger_dim, T = int(larger_dim), int(number_of_frames)
+    if norm_Scoord_func is None:
+        norm_Scoord_func = lambda x: x / (larger_dim / 2) - 1  # noqa: E731
+    if norm_Tcoord_func is None:
+        norm_Tcoord_func = lambda x: x / (T / 2) - 1  # noqa: E731
+    if device is None:
+        device = next(FG_UV_Mapping.parameters()).device
+    with open(source_point_path, 'r') as fr:
+        source_point_dict = json.load(fr)
+    keyframe_timestep = int(os.path.splitext(os.path.basename(source_point_path))[0])
+    with open(target_point_path, 'r') as fr:
+        target_point_dict = json.load(fr)
+    source_tap = formats._load(source_tap_path)
+    pred_tracks, point_name2id = source_tap['pred_tracks'].clone(), source_tap['point_name2id']
+    if T > pred_tracks.shape[0]:
+        raise formats.FormatError(f'{source_tap_path}: {pred_tracks.shape[0]} frames of tracks, the atlas has {T}')
+
+    names = [k for k in source_point_dict if k in target_point_dict]
+    details = {'names': names}
+    if names:
+        idx = torch.tensor([int(point_name2id[k]) for k in names])
+        src = [[source_point_dict[k][1], source_point_dict[k][0]] for k in names]                  # [y, x] -> (x, y)
+        tgt = [[target_point_dict[k][1], target_point_dict[k][0]] for k in names]
+        with torch.no_grad():
+            warp_xy, alpha = propagate_point(src, tgt, keyframe_timestep, T, FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha,
+                                             norm_Scoord_func, norm_Tcoord_func, device)
+        pixels = (warp_xy + 1) / 2 * larger_dim                                                    # [P, T, 2], before rounding
+        visible = alpha > 0.5
+        new = torch.where(visible.unsqueeze(-1), torch.round(pixels), torch.full_like(pixels, -1.0))
+        pred_tracks[:, idx, :] = -1
+        pred_tracks[:T, idx, :] = new.permute(1, 0, 2).to(pred_tracks.dtype).cpu()
+        details.update(pixels=pixels.cpu(), alpha=alpha.cpu())
+    out = dict(source_tap)
+    out['pred_tracks'] = pred_tracks
+    return (out, details) if return_details else out

@@ -781,6 +781,39 @@ def dift_cosine_map(feat, size, query, want_map=True):
     return cmap, yx, val
 
 
+_COORD_PE = {'none': 0, 'encoding': 1, 'hash_encoding': 2}
+_COORD_MLP = {'origin': 0, 'tcnn': 1}
+
+
+def coord_mlp(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type='none', pe_dim=0, mlp_type='origin',
+              skip_layers=(), use_tanh=True):
+    """The whole network of IMLP_Hash.forward (mlp_type 'origin') in one launch, fp32 throughout: x fp32 [N, input_dim]
+    -> fp32 [N, output_dim].  `packed`: the weights and biases in the kernel's layout (atlas.pack_coord_mlp; vsx.h K13).
+    Options the kernel does not implement raise NotImplementedError."""
+    if pe_type not in _COORD_PE:
+        raise NotImplementedError(f'coord_mlp: pe_type {pe_type!r} (IMLP_Hash knows none / encoding / hash_encoding)')
+    if mlp_type not in _COORD_MLP:
+        raise NotImplementedError(f'coord_mlp: mlp_type {mlp_type!r} (IMLP_Hash knows origin / tcnn)')
+    _chk(x, 'x', torch.float32)
+    _chk(packed, 'packed', torch.float32)
+    if x.dim() != 2 or x.shape[1] != input_dim:
+        raise _lib.VsxError(f'coord_mlp: x must be [N, {input_dim}], got {tuple(x.shape)}')
+    mask = 0
+    for i in skip_layers:
+        if not 0 <= int(i) < 62:
+            raise NotImplementedError(f'coord_mlp: skip_layers {list(skip_layers)}')
+        mask |= 1 << int(i)
+    out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    rc = lib.vsx_coord_mlp_f32(_p(x), x.shape[0], int(input_dim), int(output_dim), int(hidden_dim), int(mlp_layers),
+                               _COORD_PE[pe_type], int(pe_dim), _COORD_MLP[mlp_type], mask, int(bool(use_tanh)),
+                               _p(packed), packed.numel(), _p(out), _stream())
+    if rc == _lib.VSX_E_UNSUPPORTED:
+        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
+    check(rc, 'vsx_coord_mlp_f32')
+    return out
+
+
 _options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0'))}
 
 
@@ -1002,7 +1035,7 @@ _ACTIVATIONS = {
 }
 _PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
-          'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map')
+          'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp')
 
 
 def _publish(name):
