@@ -137,7 +137,8 @@ int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream);
 /* parts per row the launch described by d would write into d->rowstats (see above); the answer does not depend on
    d->rowstats / d->rowstats_parts themselves */
 int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d);
-/* bytes of `workspace` that make split-K possible for this problem (0: it would not be split) */
+/* bytes of `workspace` with which vsx_gemm_f16(d) takes the split-K path under the current options; 0: it would not split whatever it
+   is given (another kernel takes the problem, or d does not pass the checks of vsx_gemm_f16) */
 int64_t vsx_gemm_workspace(const vsx_gemm_desc* d);
 
 /* ------------------------------------------------------------------------------------------

@@ -943,3 +943,33 @@ def test_weight_stationary_column_slices_with_the_folded_layernorm(M, N, pe, wav
         xn = xn + pet[:frames].float().repeat_interleave(rpf, 0)
     ref = xn @ w.float().t() + b.float()
     assert float((outs[1].float() - ref).norm() / ref.norm()) < 2e-3
+
+
+def test_profiler_brackets_gemm_launches_with_their_algorithmic_work():
+    """The hipEvent profiler around vsx_gemm_f16 (csrc/prof.cpp; the CPU harness stubs the events): two sampled launches — one tile
+    launch, one split-K launch (tile kernel + combine inside ONE bracket) — are counted once each, with the closed forms of their
+    algorithmic work, 2 M N K FLOP and 2 (M K + N K + M N) bytes, and a collect empties the sample list."""
+    from videoswap_amd import ops
+    M, N = 256, 320
+    g = torch.Generator(device=DEV).manual_seed(26)
+    outs, refs = [], []
+    try:
+        ops.prof_enable(True, 8)
+        for K, tune in ((64, 0), (1536, 2 << 8)):
+            x = torch.randn(M, K, device=DEV, generator=g).half()
+            w = (torch.randn(N, K, device=DEV, generator=g) * K ** -0.5).half()
+            ops.set_option('tile_tune', tune)
+            outs.append(ops.linear(x, w))
+            refs.append(x.float() @ w.float().t())
+        r = ops.prof_collect_roofline(2.5e15, 8e12)
+        again = ops.prof_collect_roofline(2.5e15, 8e12)
+    finally:
+        ops.set_option('tile_tune', 0)
+        ops.prof_enable(False)
+    assert r['n'] == 2
+    assert r['flop'] == 2.0 * M * N * (64 + 1536)
+    assert r['bytes'] == sum(2.0 * (M * K + N * K + M * N) for K in (64, 1536))
+    assert r['ms'] > 0
+    assert again['n'] == 0
+    for y, ref in zip(outs, refs):
+        assert float((y.float() - ref).norm() / ref.norm()) < 2e-3

@@ -1,7 +1,7 @@
 // Runs vsx_gemm_f16 — the C-ABI entry point with its shape checks, dispatch, the workgroup-per-tile kernels (gemm.hip), the
 // persistent kernel (gemm_pp.hip) and the split-K combine — on the CPU from the real sources, and compares every case with a
 // double-precision GEMM / convolution.  What check_gemm_pp.cpp is for the persistent kernel alone, this is for the whole
-// entry point: dispatch thresholds, tile-kernel epilogues (row-per-lane layout, permlane32 exchange, prefetched residual and
+// entry point: dispatch thresholds (case 26: the plan of every UNet shape, pinned), tile-kernel epilogues (row-per-lane layout, permlane32 exchange, prefetched residual and
 // bias), GEGLU, the transposed V^T store, split-K + combine, the LayerNorm fold.  See hip_gemm.h for what the emulation
 // covers and what it cannot (asynchronous ordering of the LDS-DMA, register pressure, speed).
 #define CPUHIP_DYNAMIC_LDS_ONLY
@@ -59,6 +59,8 @@ namespace {
 CPUHIP_DEFINE_LDS
 }
 #include "gemm.hip"
+#include "options.cpp"
+#include "prof.cpp"
 
 
 static unsigned rng_state = 4242u;
@@ -88,6 +90,20 @@ static void report(const char* name, int rc, const std::vector<double>& want, co
     cpuhip_oob_reads = 0;
 }
 
+// vsx_gemm_f16 through its three pieces, for the checks that look at what the launch made of the plan: *xcd_gm receives the XCD block
+// grid of the tile launch (-1: another kernel family ran)
+static int gemm_by_pieces(const vsx_gemm_desc& d, int* xcd_gm) {
+    GemmParams p;
+    int rc = fill_params(&d, p);
+    if (rc != VSX_OK) return rc;
+    const GemmPlan plan = plan_gemm(d, p, false);
+    if (plan.refused) return VSX_E_UNSUPPORTED;
+    if (plan.forced || plan.splits > 1) p.ws = (float*)d.workspace;
+    rc = run_plan(plan, p, nullptr);
+    *xcd_gm = plan.family == GEMM_TILE ? p.xcd_gm : -1;
+    return rc;
+}
+
 struct Plain {
     const char* name;
     long M, N, K;
@@ -98,7 +114,7 @@ struct Plain {
 };
 
 // plain GEMM through the public entry point, every epilogue kind of the descriptor
-static std::vector<half_t> run_plain(const Plain& c, bool check = true) {
+static std::vector<half_t> run_plain(const Plain& c, bool check = true, int* xcd_gm = nullptr) {
     const long brows = c.geglu ? 2 * c.N : c.N;
     auto A = randh((size_t)c.M * c.K), B = randh((size_t)brows * c.K, 1.0f / sqrtf((float)c.K)), bias = randh(brows);
     auto R = randh((size_t)c.M * c.N);
@@ -143,7 +159,7 @@ static std::vector<half_t> run_plain(const Plain& c, bool check = true) {
     }
     (void)nimg;
     vsx_set_option("gemm_pp", c.pp);
-    const int rc = vsx_gemm_f16(&d, nullptr);
+    const int rc = xcd_gm ? gemm_by_pieces(d, xcd_gm) : vsx_gemm_f16(&d, nullptr);
     if (check) report(c.name, rc, want, C);
     return C;
 }
@@ -228,7 +244,7 @@ static void run_subpixel(const char* name, int nimg, int Hs, int Ws, int C, int 
 
 // 3x3 / 1x1 convolution with bias + time-embedding row vector + residual (both addends: the tile kernels)
 static std::vector<half_t> run_conv(const char* name, int nimg, int H, int W, int C1, int C2, int Cout, int ks, int stride, int ups, bool splitk,
-                                    long pp = 1, bool both_addends = true) {
+                                    long pp = 1, bool both_addends = true, int* xcd_gm = nullptr) {
     const int pad = ks / 2;
     const int Hs = ups ? H / 2 : H, Ws = ups ? W / 2 : W;
     const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
@@ -272,8 +288,117 @@ static std::vector<half_t> run_conv(const char* name, int nimg, int H, int W, in
         d.workspace = ws.data(); d.workspace_bytes = bytes;
     }
     vsx_set_option("gemm_pp", pp);
-    report(name, vsx_gemm_f16(&d, nullptr), want, C);
+    report(name, xcd_gm ? gemm_by_pieces(d, xcd_gm) : vsx_gemm_f16(&d, nullptr), want, C);
     return C;
+}
+
+// ---- case 26: the plan table ----
+enum { PR_RES = 1, PR_ROWVEC = 2, PR_GEGLU = 4, PR_LN = 8, PR_VT = 16, PR_STATS = 32, PR_STATS_BAD = 64, PR_BIAS_ODD = 128 };
+struct PlanRow {
+    const char* name;
+    long M, N, K;                                   // plain GEMM (M < 0: -M batches of 40 rows); a convolution derives M and K
+    long nimg, H, W, C1, C2, ks, stride, ups;       // convolution (ks > 0)
+    long flags;                                     // PR_*
+    long pp, ws, ws_waves, tune;                    // options gemm_pp, gemm_ws, ws_waves, tile_tune
+    // expected plan
+    int family, BM, BN, WAVES_M, WAVES_N, deep, splits, nk_per;
+    long stat_parts;
+    long long workspace_bytes;
+    int refused;
+};
+
+// The descriptor of a row.  No operand is ever touched (the plan is made from shapes, strides and alignments), so the pointers
+// are made-up addresses with the alignment the row asks for.
+static vsx_gemm_desc plan_desc(const PlanRow& r) {
+    char* const mem = reinterpret_cast<char*>(0x10000000);
+    vsx_gemm_desc d{};
+    d.batch0 = d.batch1 = 1;
+    d.N = r.N;
+    d.A = mem; d.B = mem + 0x1000; d.C = mem + 0x2000;
+    d.bias = mem + 0x3000 + ((r.flags & PR_BIAS_ODD) ? 2 : 0);
+    d.alpha = 1.0; d.pad_lo = d.pad_hi = -1;
+    d.geglu = (r.flags & PR_GEGLU) ? 1 : 0;
+    long rows_per_vec = 32;
+    if (r.ks > 0) {
+        const long pad = r.ks / 2;
+        const long Ho = (r.H + 2 * pad - r.ks) / r.stride + 1, Wo = (r.W + 2 * pad - r.ks) / r.stride + 1;
+        d.M = r.nimg * Ho * Wo;
+        d.K = r.ks * r.ks * (r.C1 + r.C2);
+        d.a_mode = 1; d.H = r.H; d.W = r.W; d.C1 = r.C1; d.C2 = r.C2; d.ks = r.ks; d.stride = r.stride; d.upsample = r.ups;
+        if (r.C2) d.A2 = mem + 0x4000;
+        rows_per_vec = Ho * Wo;
+    } else if (r.M < 0) {
+        d.M = 40; d.K = r.K; d.batch0 = 2; d.batch1 = -r.M / 2;
+        d.lda = d.K; d.a_bs1 = d.M * d.K; d.a_bs0 = d.batch1 * d.a_bs1;
+        d.b_bs1 = d.N * d.K; d.b_bs0 = d.batch1 * d.b_bs1;
+        d.c_bs1 = d.M * d.N; d.c_bs0 = d.batch1 * d.c_bs1;
+    } else {
+        d.M = r.M; d.K = r.K; d.lda = r.K;
+    }
+    d.ldb = d.K;
+    d.ldc = d.N;
+    if (r.flags & PR_VT) {
+        const long rpi = d.K == 768 ? 77 : d.N == 320 ? 4096 : d.N == 640 ? 1024 : 256;     // text tokens, or the pixels of the UNet level
+        d.c_mode = 1; d.c_rows_per_img = rpi; d.ldc = rpi; d.c_img_stride = d.N * rpi;
+    }
+    if (r.flags & PR_RES) { d.residual = mem + 0x5000; d.ldr = d.N; }
+    if (r.flags & PR_ROWVEC) { d.rowvec = mem + 0x6000; d.rows_per_vec = rows_per_vec; }
+    if (r.flags & PR_LN) { d.rowscale = mem + 0x7000; d.colvec = mem + 0x8000; }
+    return d;
+}
+
+static void plan_options(const PlanRow& r) {
+    vsx_set_option("gemm_pp", r.pp);
+    vsx_set_option("gemm_ws", r.ws);
+    vsx_set_option("ws_waves", r.ws_waves);
+    vsx_set_option("tile_tune", r.tune);
+}
+
+// The plan of every row of gemm_plan_rows.inc (made from the launches of the revision before plan_gemm: see that file), and the two
+// query functions against it.  Nothing is launched: "the launch" below is plan_gemm(..., assume_workspace = false), which is all
+// vsx_gemm_f16 consults.
+static void check_plans() {
+    static const PlanRow rows[] = {
+#include "gemm_plan_rows.inc"
+    };
+    int bad = 0, nsplit = 0;
+    for (const PlanRow& r : rows) {
+        plan_options(r);
+        vsx_gemm_desc d = plan_desc(r);
+        const int64_t parts = vsx_gemm_rowstats_parts(&d), bytes = vsx_gemm_workspace(&d);
+        if (r.flags & (PR_STATS | PR_STATS_BAD)) { d.rowstats = (char*)d.A + 0x9000; d.rowstats_parts = parts + ((r.flags & PR_STATS_BAD) ? 1 : 0); }
+        d.workspace = (char*)d.A + 0xA000;
+        d.workspace_bytes = bytes;
+        GemmParams p;
+        const int rc = fill_params(&d, p);
+        const GemmPlan plan = plan_gemm(d, p, false), asked = plan_gemm(d, p, true);
+        bool ok = rc == VSX_OK && (int)plan.refused == r.refused && plan.stat_parts == r.stat_parts && parts == r.stat_parts &&
+                  plan.workspace_bytes == r.workspace_bytes && asked.workspace_bytes == r.workspace_bytes && bytes == r.workspace_bytes &&
+                  vsx_gemm_rowstats_parts(&d) == r.stat_parts && plan.splits == r.splits && plan.nk_per == r.nk_per;
+        if (!r.refused) {
+            ok = ok && (int)plan.family == r.family;
+            if (r.family == GEMM_TILE)
+                ok = ok && plan.BM == r.BM && plan.BN == r.BN && plan.WAVES_M == r.WAVES_M && plan.WAVES_N == r.WAVES_N && (int)plan.deep == r.deep;
+        }
+        if (r.splits > 1) {          // exactly the bytes asked for: split (above); one byte fewer, or no workspace at all: not split
+            ++nsplit;
+            d.workspace_bytes = bytes - 1;
+            const GemmPlan shortp = plan_gemm(d, p, false);
+            d.workspace = nullptr; d.workspace_bytes = bytes;
+            const GemmPlan none = plan_gemm(d, p, false);
+            ok = ok && shortp.splits == 1 && none.splits == 1 && shortp.family == GEMM_TILE && shortp.workspace_bytes == bytes;
+        }
+        if (!ok) {
+            ++bad;
+            printf("  plan of '%s': rc %d family %d tile %dx%d (%d x %d waves) deep %d splits %d x %d slabs, %ld parts (asked: %ld), %lld bytes (asked: %lld), refused %d  FAIL\n",
+                   r.name, rc, (int)plan.family, plan.BM, plan.BN, plan.WAVES_M, plan.WAVES_N, (int)plan.deep, plan.splits, plan.nk_per,
+                   plan.stat_parts, (long)parts, (long long)plan.workspace_bytes, (long long)bytes, (int)plan.refused);
+        }
+    }
+    plan_options(PlanRow{"defaults", 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 10, 0});
+    const int n = (int)(sizeof(rows) / sizeof(rows[0]));
+    printf("%-58s %d rows, %d split-K %s\n", "pinned plans (gemm_plan_rows.inc)", n, nsplit, bad == 0 && nsplit > 0 ? "ok" : "FAIL");
+    n_bad += bad + (nsplit > 0 ? 0 : 1);
 }
 
 int main(int argc, char** argv) {
@@ -344,12 +469,11 @@ int main(int argc, char** argv) {
             vsx_set_option("tile_tune", g.tune);
             vsx_set_option("xcd_walk", 0);
             rng_state = 1234u;
-            const auto a = run_plain(c, false);
-            const int gm0 = g_last_xcd_gm;
+            int gm0 = -1, gm1 = -1;
+            const auto a = run_plain(c, false, &gm0);
             vsx_set_option("xcd_walk", 1);
             rng_state = 1234u;
-            const auto b = run_plain(c, true);
-            const int gm1 = g_last_xcd_gm;
+            const auto b = run_plain(c, true, &gm1);
             const bool same = memcmp(a.data(), b.data(), a.size() * sizeof(half_t)) == 0;
             printf("%-58s %s (gm %d -> %d)\n", "  ... bit-identical to the linear walk, grid chosen", same && gm0 == 0 && gm1 == g.want_gm ? "ok" : "FAIL", gm0, gm1);
             n_bad += same && gm0 == 0 && gm1 == g.want_gm ? 0 : 1;
@@ -361,10 +485,11 @@ int main(int argc, char** argv) {
         const auto a = run_conv("conv3x3 8x8x8 192->640, 128x320 tiles x 2 K slices, linear walk", 8, 8, 8, 192, 0, 640, 3, 1, 0, true, 0, true);
         vsx_set_option("xcd_walk", 1);
         rng_state = 77u;
-        const auto b = run_conv("conv3x3 8x8x8 192->640, 128x320 tiles x 2 K slices, XCD block grid", 8, 8, 8, 192, 0, 640, 3, 1, 0, true, 0, true);
+        int gm = -1;
+        const auto b = run_conv("conv3x3 8x8x8 192->640, 128x320 tiles x 2 K slices, XCD block grid", 8, 8, 8, 192, 0, 640, 3, 1, 0, true, 0, true, &gm);
         const bool same = memcmp(a.data(), b.data(), a.size() * sizeof(half_t)) == 0;
-        printf("%-58s %s (gm %d)\n", "  ... bit-identical, grid chosen", same && g_last_xcd_gm > 0 ? "ok" : "FAIL", g_last_xcd_gm);
-        n_bad += same && g_last_xcd_gm > 0 ? 0 : 1;
+        printf("%-58s %s (gm %d)\n", "  ... bit-identical, grid chosen", same && gm > 0 ? "ok" : "FAIL", gm);
+        n_bad += same && gm > 0 ? 0 : 1;
         }
         vsx_set_option("tile_tune", 0);
         vsx_set_option("xcd_walk", 1);
@@ -497,6 +622,7 @@ int main(int argc, char** argv) {
         }
         vsx_set_option("gemm_pp", 1);
     }
+    if (only < 0 || only == nplain + 13) check_plans();      // which kernel every UNet shape, threshold and option value gets
     printf(n_bad ? "%d check(s) FAILED\n" : "all checks passed\n", n_bad);
     return n_bad ? 1 : 0;
 }

@@ -22,8 +22,9 @@ static inline float __shfl_down(float v, int delta, int width = 64) {
     return r;
 }
 static long g_gn_fuse = 1;
+#include "options.h"
 namespace vsxg {
-long gemm_option(const char*) { return g_gn_fuse; }      // the option table lives in gemm.hip: only "gn_fuse" is asked here
+long gemm_option(const char*) { return g_gn_fuse; }      // stands in for the option table (options.cpp): only "gn_fuse" is asked here
 }
 
 int vsx_fail(int code, const char* fmt, ...) {

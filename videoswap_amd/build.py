@@ -30,7 +30,7 @@ LIB = os.path.join(LIBDIR, 'libvsx.so')
 VARIANTS = {}
 # variant name -> additional sources (relative to csrc/)
 VARIANT_EXTRA = {}
-SOURCES = ['api.cpp', 'comm.cpp', 'gemm.hip', 'gemm_pp.hip', 'norm.hip', 'attention.hip', 'attention_bwd.hip', 'elementwise.hip',
+SOURCES = ['api.cpp', 'comm.cpp', 'options.cpp', 'prof.cpp', 'gemm.hip', 'gemm_pp.hip', 'norm.hip', 'attention.hip', 'attention_bwd.hip', 'elementwise.hip',
            'train.hip', 'dift.hip', 'atlas.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-x', 'hip',

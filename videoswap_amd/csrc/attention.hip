@@ -19,12 +19,9 @@
 //      r with bits 2,3 swapped, which makes a lane's 8 scores per MFMA step 8 consecutive keys;
 //      V^T tile [DT*32][72] halfs (144-byte rows = 9 slots, odd => conflict-free b128 reads).
 #include "common.h"
+#include "options.h"
 
 #include <type_traits>
-
-namespace vsxg {
-long gemm_option(const char* name);      // gemm.hip: the option table of vsx_set_option
-}
 
 namespace {
 

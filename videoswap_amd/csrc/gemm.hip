@@ -31,9 +31,9 @@
 // transposed store (V^T for the attention kernel).  Accumulators hold C^T (SWAP) so a lane owns one output row and 4
 // consecutive columns per register quad: 8-byte vector loads/stores in the epilogue.
 #include "gemm_common.h"
+#include "prof.h"
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
 #include <stdlib.h>
 #include <string.h>
 
@@ -900,8 +900,6 @@ inline int plan_splitk(const vsx_gemm_desc* d, long tiles, bool eligible) {
     return s;
 }
 
-int g_last_xcd_gm = 0;       // diagnostics (tools/cpu_check/check_gemm_api.cpp reads it): the arrangement of the last tile-kernel launch
-
 // XCD BLOCK GRID (gemm_kernel): which gm x (8 / gm) arrangement of the XCDs over (tile_m, np) moves the fewest operand bytes
 // through the L2s.  Per XCD: (tiles_m / gm) x (K slices its column block meets) activation panels + NP * gm / 8 weight
 // panels.  Returns 0 (the linear walk: the same blocks as gm = 8 whenever tiles_m is a multiple of 8) unless another
@@ -951,7 +949,7 @@ int launch(GemmParams& p, long tiles_m, long nbatch, hipStream_t stream) {
     }
     p.pp_flags = (int)(gemm_option("pp_sched") & TILE_RES_EARLY);
     p.tiles_m = (int)tiles_m;
-    p.xcd_gm = g_last_xcd_gm = plan_xcd_grid(p, tiles_m, BM, BN, nbatch);
+    p.xcd_gm = plan_xcd_grid(p, tiles_m, BM, BN, nbatch);
     dim3 grid((unsigned)(tiles_m * p.tiles_n), 1, (unsigned)(p.splitk > 1 ? p.splitk : nbatch));
     if (p.xcd_gm > 0) grid = dim3((unsigned)(tiles_m * p.tiles_n * (p.splitk > 1 ? p.splitk : 1)), 1, 1);
     hipLaunchKernelGGL((gemm_kernel<BM, BN, WAVES_M, WAVES_N, SWAP, NSTAGE>), grid, dim3(WAVES_M * WAVES_N * 64), smem,
@@ -974,144 +972,97 @@ int launch_tile(GemmParams& p, long M, long cols, long nbatch, hipStream_t strea
     return launch<BM, BN, WAVES_M, WAVES_N, true, NST>(p, tiles_m, nbatch, stream);
 }
 
-// ---- instrumentation (bench.py roofline): hipEvent pairs around sampled launches ----
-struct ProfState {
-    bool on = false;
-    bool paused = false;
-    long max_samples = 0;
-    long stride = 1, seen = 0;
-    long n = 0;
-    double flop = 0.0;
-    std::vector<hipEvent_t>* ev = nullptr;  // 2 per sample
-    std::vector<double>* work = nullptr;    // 2 per sample: algorithmic FLOP, algorithmic bytes (vsx_prof_collect_roofline)
+// ---- dispatch: fill_params (descriptor checks) -> plan_gemm (which kernel, as data) -> run_plan (the launch) ----
+
+int pp_mode() { return (int)gemm_option("gemm_pp"); }
+
+enum GemmFamily { GEMM_WS, GEMM_PP256, GEMM_PP128, GEMM_TILE };
+enum GemmRefusal { PLAN_OK = 0, PLAN_SUBPIXEL_OFF_PP, PLAN_ROWSTATS_PARTS };
+
+// What vsx_gemm_f16 will launch for a descriptor, under the current option values.
+struct GemmPlan {
+    GemmFamily family;                  // weight-stationary, persistent 256- / 128-row tiles, or a workgroup-per-tile kernel
+    int BM, BN, WAVES_M, WAVES_N;       // GEMM_TILE: gemm_kernel<BM, BN, WAVES_M, WAVES_N, ...>
+    bool deep;                          // GEMM_TILE 128x160: four ring slots instead of two (launch_tile)
+    bool forced;                        // GEMM_TILE chosen by option tile_tune: the launch is handed the workspace pointer as it is
+    long nbatch;                        // GEMM_TILE: batch slices of the launch (batch0 * batch1)
+    int splits, nk_per;                 // split-K: slices (1 = none) and K slabs per slice
+    long stat_parts;                    // row-statistics parts per row this launch writes (0: it cannot)
+    int64_t workspace_bytes;            // what split-K needs; 0 unless the launch takes the split-K path once it has that much
+    GemmRefusal refused;                // vsx_gemm_f16 fails with VSX_E_UNSUPPORTED
 };
 
-ProfState g_prof;
-
-}  // namespace
-
-extern "C" int vsx_prof_enable(int64_t on, int64_t max_samples) {
-    if (!g_prof.ev) g_prof.ev = new std::vector<hipEvent_t>();
-    if (!g_prof.work) g_prof.work = new std::vector<double>();
-    g_prof.work->clear();
-    g_prof.on = on != 0;
-    g_prof.stride = on > 1 ? on : 1;        // on = k > 1: bracket every k-th launch only
-    g_prof.seen = 0;
-    g_prof.max_samples = max_samples;
-    g_prof.n = 0;
-    g_prof.flop = 0.0;
-    return VSX_OK;
-}
-
-// suspend / resume sampling without touching what has been collected (HIP-graph capture and replayed calls)
-extern "C" int vsx_prof_pause(int64_t paused) {
-    g_prof.paused = paused != 0;
-    return VSX_OK;
-}
-
-// Per sampled launch: duration t, algorithmic FLOP f and algorithmic bytes b (A once + weights once + C once + residual once; a
-// convolution reads every input pixel once).  A launch cannot finish before max(f / peak_flops, b / peak_bytes_per_s): the sum of
-// those floors over the samples is what the same launches would take on BOTH rooflines at once (`floor_ms`), and
-// `byte_bound_ms` is the measured time of the launches whose byte floor is the larger one.
-extern "C" int vsx_prof_collect_roofline(double peak_flops, double peak_bytes_per_s, int64_t* n_launches, double* total_ms,
-                                         double* total_flop, double* total_bytes, double* floor_ms, double* byte_bound_ms) {
-    double ms = 0.0, bytes = 0.0, floor = 0.0, bb = 0.0;
-    if (g_prof.ev) {
-        for (long i = 0; i < g_prof.n; ++i) {
-            hipEvent_t a = (*g_prof.ev)[2 * i], b = (*g_prof.ev)[2 * i + 1];
-            if (hipEventSynchronize(b) != hipSuccess) return vsx_fail(VSX_E_LAUNCH, "prof: event sync failed");
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, a, b) != hipSuccess) return vsx_fail(VSX_E_LAUNCH, "prof: elapsed failed");
-            ms += t;
-            if (g_prof.work && (long)g_prof.work->size() >= 2 * (i + 1) && peak_flops > 0.0 && peak_bytes_per_s > 0.0) {
-                const double f = (*g_prof.work)[2 * i], by = (*g_prof.work)[2 * i + 1];
-                const double tf = f / peak_flops, tb = by / peak_bytes_per_s;
-                bytes += by;
-                floor += 1e3 * (tf > tb ? tf : tb);
-                if (tb > tf) bb += t;
-            }
-        }
+// a_mode 1: the implicit-GEMM convolution's geometry and buffer extents
+int fill_conv_params(const vsx_gemm_desc* d, GemmParams& p, const long nbatch) {
+    VSX_REQUIRE(nbatch == 1, VSX_E_UNSUPPORTED, "gemm: conv mode does not take a batch");
+    VSX_REQUIRE(d->ks == 1 || d->ks == 3, VSX_E_UNSUPPORTED, "gemm: conv kernel size %ld", (long)d->ks);
+    VSX_REQUIRE(d->stride == 1 || d->stride == 2, VSX_E_UNSUPPORTED, "gemm: conv stride %ld", (long)d->stride);
+    VSX_REQUIRE(d->C1 > 0 && d->C1 % 8 == 0 && d->C2 >= 0 && d->C2 % 8 == 0, VSX_E_BADSHAPE,
+                "gemm: conv channels must be multiples of 8 (C1=%ld C2=%ld)", (long)d->C1, (long)d->C2);
+    VSX_REQUIRE((d->C2 == 0) == (d->A2 == nullptr), VSX_E_BADSHAPE, "gemm: A2/C2 mismatch");
+    VSX_REQUIRE(d->A2 == nullptr || vsx_aligned16(d->A2), VSX_E_BADSHAPE, "gemm: A2 must be 16-byte aligned");
+    VSX_REQUIRE(d->K == d->ks * d->ks * (d->C1 + d->C2), VSX_E_BADSHAPE, "gemm: conv K mismatch");
+    VSX_REQUIRE(d->C2 == 0 || (d->C1 % 64 == 0 && d->C2 % 64 == 0), VSX_E_UNSUPPORTED,
+                "gemm: a two-source conv needs both channel counts to be multiples of 64 (one K slab)");
+    VSX_REQUIRE(d->H > 0 && d->W > 0, VSX_E_BADSHAPE, "gemm: conv H/W");
+    VSX_REQUIRE(!d->upsample || (d->H % 2 == 0 && d->W % 2 == 0), VSX_E_BADSHAPE, "gemm: upsample needs even H/W");
+    p.H = (int)d->H; p.W = (int)d->W; p.C1 = (int)d->C1; p.C2 = (int)d->C2;
+    p.ks = (int)d->ks; p.stride = (int)d->stride; p.ups = d->upsample ? 1 : 0;
+    const bool subpix = d->upsample == 2;
+    if (subpix) {
+        // sub-pixel form (vsx.h: upsample = 2): internally a plain 3x3 window on the SOURCE image, four taps per class
+        VSX_REQUIRE(d->ks == 3 && d->stride == 1 && d->C2 == 0 && d->C1 % 64 == 0 && d->pad_lo < 0 && d->pad_hi < 0 &&
+                        !d->rowvec && !d->residual && !d->geglu && d->c_mode == 0 && !d->rowscale && !d->rowstats,
+                    VSX_E_UNSUPPORTED, "gemm: the sub-pixel form takes a single-source 3x3 stride-1 convolution with a bias only");
+        VSX_REQUIRE(d->M % 4 == 0, VSX_E_BADSHAPE, "gemm: sub-pixel form: M must be a multiple of 4");
+        p.ups = 0;
+        p.H = (int)d->H / 2;
+        p.W = (int)d->W / 2;
+        p.sp_Mc = (int)(d->M / 4);
+        p.K = 4 * d->C1;                 // slabs actually multiplied (the weight rows stay 9 C long: ldb)
     }
-    if (n_launches) *n_launches = g_prof.n;
-    if (total_ms) *total_ms = ms;
-    if (total_flop) *total_flop = g_prof.flop;
-    if (total_bytes) *total_bytes = bytes;
-    if (floor_ms) *floor_ms = floor;
-    if (byte_bound_ms) *byte_bound_ms = bb;
-    g_prof.n = 0;
-    g_prof.flop = 0.0;
-    if (g_prof.work) g_prof.work->clear();
+    const bool sym = d->pad_lo < 0 && d->pad_hi < 0;
+    VSX_REQUIRE(sym || (d->pad_lo >= 0 && d->pad_hi >= 0 && d->pad_lo < d->ks && d->pad_hi < d->ks), VSX_E_BADSHAPE,
+                "gemm: conv padding (%ld, %ld) for kernel size %ld", (long)d->pad_lo, (long)d->pad_hi, (long)d->ks);
+    const int pad_lo = sym ? p.ks / 2 : (int)d->pad_lo, pad_hi = sym ? p.ks / 2 : (int)d->pad_hi;
+    p.pad = pad_lo;
+    p.Ho = (p.H + pad_lo + pad_hi - p.ks) / p.stride + 1;
+    p.Wo = (p.W + pad_lo + pad_hi - p.ks) / p.stride + 1;
+    {
+        const long pix = (d->M / ((long)p.Ho * p.Wo) / (subpix ? 4 : 1)) * (long)(p.ups ? p.H / 2 : p.H) * (p.ups ? p.W / 2 : p.W);
+        VSX_REQUIRE(pix * d->C1 * 2 < (1L << 31) && pix * d->C2 * 2 < (1L << 31), VSX_E_UNSUPPORTED,
+                    "gemm: conv source tensors must be smaller than 2 GiB");
+        p.a_bytes = (unsigned)(pix * d->C1 * 2);
+        p.a2_bytes = (unsigned)(pix * d->C2 * 2);
+    }
+    VSX_REQUIRE(d->M % ((long)p.Ho * p.Wo) == 0, VSX_E_BADSHAPE, "gemm: conv M (%ld) not a multiple of Ho*Wo (%d*%d)",
+                (long)d->M, p.Ho, p.Wo);
+    if (subpix) {                        // B = four [N, 9 C] matrices, one per (ph, pw) class
+        const long bb = ((4 * d->N - 1) * d->ldb + d->K) * 2;
+        VSX_REQUIRE(bb < (1L << 31), VSX_E_UNSUPPORTED, "gemm: B operand slice must be smaller than 2 GiB");
+        p.b_bytes = (unsigned)bb;
+    }
     return VSX_OK;
 }
 
-extern "C" int vsx_prof_collect(int64_t* n_launches, double* total_ms, double* total_flop) {
-    return vsx_prof_collect_roofline(0.0, 0.0, n_launches, total_ms, total_flop, nullptr, nullptr, nullptr);
+// vector widths of the epilogue's loads and stores
+void fill_vector_widths(const vsx_gemm_desc* d, GemmParams& p) {
+    // 8-byte vector epilogue when every row start / column quad is 8-byte aligned
+    auto al8 = [](const void* q) { return (((uintptr_t)q) & 7) == 0; };
+    p.vec4 = (d->ldc % 4 == 0 && d->c_bs0 % 4 == 0 && d->c_bs1 % 4 == 0 && al8(d->C) && al8(d->bias) &&
+              al8(d->rowvec) && d->N % 4 == 0 &&
+              (!d->residual || (al8(d->residual) && d->ldr % 4 == 0 && d->r_bs0 % 4 == 0 && d->r_bs1 % 4 == 0)))
+                 ? 1 : 0;
+    // 16-byte stores (two lanes of a pair exchange register quads first) when rows and column octets are 16-byte aligned
+    auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+    p.vec8 = (p.vec4 && d->ldc % 8 == 0 && d->c_bs0 % 8 == 0 && d->c_bs1 % 8 == 0 && al16(d->C) && d->N % 8 == 0) ? 1 : 0;
+    p.rvec8 = (p.vec8 && d->residual && al16(d->residual) && d->ldr % 8 == 0 && d->r_bs0 % 8 == 0 && d->r_bs1 % 8 == 0)
+                  ? 1 : 0;
 }
 
-namespace vsxg {
-namespace {
-struct Option { const char* name; const char* env; long value; bool init; };
-Option g_options[] = {{"gemm_pp", "VSX_GEMM_PP", 1, false}, {"pp_sched", "VSX_PP_SCHED", 0, false},
-                      {"tile_tune", "VSX_TUNE_TILE", 0, false}, {"xcd_walk", "VSX_XCD_WALK", 1, false},
-                      {"attn_qb", "VSX_ATTN_QB", 0, false}, {"temporal_out", "VSX_TEMPORAL_OUT", 0, false},
-                      {"attn_o16", "VSX_ATTN_O16", 0, false}, {"gn_fuse", "VSX_GN_FUSE", 0, false},
-                      {"gemm_ws", "VSX_GEMM_WS", 1, false}, {"ws_waves", "VSX_WS_WAVES", 10, false}};
-Option* find_option(const char* name) {
-    for (auto& o : g_options)
-        if (strcmp(o.name, name) == 0) {
-            if (!o.init) {
-                const char* e = getenv(o.env);
-                if (e) o.value = atol(e);
-                o.init = true;
-            }
-            return &o;
-        }
-    return nullptr;
-}
-}  // namespace
-long gemm_option(const char* name) {
-    Option* o = find_option(name);
-    return o ? o->value : 0;
-}
-}  // namespace vsxg
-
-extern "C" int vsx_set_option(const char* name, int64_t value) {
-    auto* o = name ? vsxg::find_option(name) : nullptr;
-    if (!o) return vsx_fail(VSX_E_BADSHAPE, "vsx_set_option: unknown option '%s'", name ? name : "(null)");
-    o->value = (long)value;
-    return VSX_OK;
-}
-
-static int pp_mode() { return (int)vsxg::gemm_option("gemm_pp"); }
-
-extern "C" int64_t vsx_gemm_workspace(const vsx_gemm_desc* d) {
-    if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-    const long nbatch = d->batch0 * d->batch1;
-    const long cols = d->geglu ? 2 * d->N : d->N;
-    const bool vec4 = d->ldc % 4 == 0 && d->N % 4 == 0 && (!d->residual || d->ldr % 4 == 0);
-    const bool eligible = cols % 320 == 0 && nbatch == 1 && !d->geglu && d->c_mode == 0 && vec4;
-    const long tiles = ((d->M + 127) / 128) * ((cols + 319) / 320);
-    const int s = plan_splitk(d, tiles, eligible);
-    return s > 1 ? (int64_t)s * d->M * d->N * (int64_t)sizeof(float) : 0;
-}
-
-static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, bool dry, int64_t* parts_out);
-
-extern "C" int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream) { return gemm_impl(d, stream, false, nullptr); }
-
-// How many row-statistics parts would this launch write?  The same checks and the same kernel choice as the launch itself
-// (gemm_impl stops in front of it); 0 whenever the problem does not go to the persistent kernel with an eligible epilogue.
-extern "C" int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d) {
-    int64_t parts = 0;
-    if (!d || d->M <= 0) return 0;
-    vsx_gemm_desc probe = *d;
-    probe.rowstats = nullptr;
-    probe.rowstats_parts = 0;
-    return gemm_impl(&probe, nullptr, true, &parts) == VSX_OK ? parts : 0;
-}
-
-static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, const bool dry, int64_t* parts_out) {
-    hipStream_t stream = (hipStream_t)stream_;
+// Every check of the descriptor, and the kernel parameters it describes.  No HIP call.  VSX_OK with d->M == 0 means "nothing to
+// launch" (p is then not filled).  The row statistics and the workspace are bound by the launch, once the plan is known.
+int fill_params(const vsx_gemm_desc* d, GemmParams& p) {
     VSX_REQUIRE(d != nullptr, VSX_E_BADSHAPE, "gemm: null descriptor");
     VSX_REQUIRE(d->M >= 0 && d->N > 0 && d->K > 0, VSX_E_BADSHAPE, "gemm: bad M/N/K %ld/%ld/%ld",
                 (long)d->M, (long)d->N, (long)d->K);
@@ -1125,7 +1076,7 @@ static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, const bool dr
     VSX_REQUIRE(d->b_bs0 % 8 == 0 && d->b_bs1 % 8 == 0 && d->a_bs0 % 8 == 0 && d->a_bs1 % 8 == 0, VSX_E_BADSHAPE,
                 "gemm: batch strides must be multiples of 8 elements");
 
-    GemmParams p{};
+    p = GemmParams{};
     p.A = (const half_t*)d->A;
     p.A2 = (const half_t*)d->A2;
     p.B = (const half_t*)d->B;
@@ -1172,54 +1123,8 @@ static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, const bool dr
         p.a_bytes = (unsigned)ab;
         p.a2_bytes = 0;
     } else if (p.a_mode == 1) {
-        VSX_REQUIRE(nbatch == 1, VSX_E_UNSUPPORTED, "gemm: conv mode does not take a batch");
-        VSX_REQUIRE(d->ks == 1 || d->ks == 3, VSX_E_UNSUPPORTED, "gemm: conv kernel size %ld", (long)d->ks);
-        VSX_REQUIRE(d->stride == 1 || d->stride == 2, VSX_E_UNSUPPORTED, "gemm: conv stride %ld", (long)d->stride);
-        VSX_REQUIRE(d->C1 > 0 && d->C1 % 8 == 0 && d->C2 >= 0 && d->C2 % 8 == 0, VSX_E_BADSHAPE,
-                    "gemm: conv channels must be multiples of 8 (C1=%ld C2=%ld)", (long)d->C1, (long)d->C2);
-        VSX_REQUIRE((d->C2 == 0) == (d->A2 == nullptr), VSX_E_BADSHAPE, "gemm: A2/C2 mismatch");
-        VSX_REQUIRE(d->A2 == nullptr || vsx_aligned16(d->A2), VSX_E_BADSHAPE, "gemm: A2 must be 16-byte aligned");
-        VSX_REQUIRE(d->K == d->ks * d->ks * (d->C1 + d->C2), VSX_E_BADSHAPE, "gemm: conv K mismatch");
-        VSX_REQUIRE(d->C2 == 0 || (d->C1 % 64 == 0 && d->C2 % 64 == 0), VSX_E_UNSUPPORTED,
-                    "gemm: a two-source conv needs both channel counts to be multiples of 64 (one K slab)");
-        VSX_REQUIRE(d->H > 0 && d->W > 0, VSX_E_BADSHAPE, "gemm: conv H/W");
-        VSX_REQUIRE(!d->upsample || (d->H % 2 == 0 && d->W % 2 == 0), VSX_E_BADSHAPE, "gemm: upsample needs even H/W");
-        p.H = (int)d->H; p.W = (int)d->W; p.C1 = (int)d->C1; p.C2 = (int)d->C2;
-        p.ks = (int)d->ks; p.stride = (int)d->stride; p.ups = d->upsample ? 1 : 0;
-        const bool subpix = d->upsample == 2;
-        if (subpix) {
-            // sub-pixel form (vsx.h: upsample = 2): internally a plain 3x3 window on the SOURCE image, four taps per class
-            VSX_REQUIRE(d->ks == 3 && d->stride == 1 && d->C2 == 0 && d->C1 % 64 == 0 && d->pad_lo < 0 && d->pad_hi < 0 &&
-                            !d->rowvec && !d->residual && !d->geglu && d->c_mode == 0 && !d->rowscale && !d->rowstats,
-                        VSX_E_UNSUPPORTED, "gemm: the sub-pixel form takes a single-source 3x3 stride-1 convolution with a bias only");
-            VSX_REQUIRE(d->M % 4 == 0, VSX_E_BADSHAPE, "gemm: sub-pixel form: M must be a multiple of 4");
-            p.ups = 0;
-            p.H = (int)d->H / 2;
-            p.W = (int)d->W / 2;
-            p.sp_Mc = (int)(d->M / 4);
-            p.K = 4 * d->C1;                 // slabs actually multiplied (the weight rows stay 9 C long: ldb)
-        }
-        const bool sym = d->pad_lo < 0 && d->pad_hi < 0;
-        VSX_REQUIRE(sym || (d->pad_lo >= 0 && d->pad_hi >= 0 && d->pad_lo < d->ks && d->pad_hi < d->ks), VSX_E_BADSHAPE,
-                    "gemm: conv padding (%ld, %ld) for kernel size %ld", (long)d->pad_lo, (long)d->pad_hi, (long)d->ks);
-        const int pad_lo = sym ? p.ks / 2 : (int)d->pad_lo, pad_hi = sym ? p.ks / 2 : (int)d->pad_hi;
-        p.pad = pad_lo;
-        p.Ho = (p.H + pad_lo + pad_hi - p.ks) / p.stride + 1;
-        p.Wo = (p.W + pad_lo + pad_hi - p.ks) / p.stride + 1;
-        {
-            const long pix = (d->M / ((long)p.Ho * p.Wo) / (subpix ? 4 : 1)) * (long)(p.ups ? p.H / 2 : p.H) * (p.ups ? p.W / 2 : p.W);
-            VSX_REQUIRE(pix * d->C1 * 2 < (1L << 31) && pix * d->C2 * 2 < (1L << 31), VSX_E_UNSUPPORTED,
-                        "gemm: conv source tensors must be smaller than 2 GiB");
-            p.a_bytes = (unsigned)(pix * d->C1 * 2);
-            p.a2_bytes = (unsigned)(pix * d->C2 * 2);
-        }
-        VSX_REQUIRE(d->M % ((long)p.Ho * p.Wo) == 0, VSX_E_BADSHAPE, "gemm: conv M (%ld) not a multiple of Ho*Wo (%d*%d)",
-                    (long)d->M, p.Ho, p.Wo);
-        if (subpix) {                        // B = four [N, 9 C] matrices, one per (ph, pw) class
-            const long bb = ((4 * d->N - 1) * d->ldb + d->K) * 2;
-            VSX_REQUIRE(bb < (1L << 31), VSX_E_UNSUPPORTED, "gemm: B operand slice must be smaller than 2 GiB");
-            p.b_bytes = (unsigned)bb;
-        }
+        const int rc = fill_conv_params(d, p, nbatch);
+        if (rc != VSX_OK) return rc;
     } else {
         return vsx_fail(VSX_E_UNSUPPORTED, "gemm: a_mode %d", p.a_mode);
     }
@@ -1230,40 +1135,75 @@ static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, const bool dr
                      d->c_bs0 % 4 == 0 && d->c_bs1 % 4 == 0) ? 1 : 0;
     }
     if (p.geglu) VSX_REQUIRE(!d->rowvec, VSX_E_UNSUPPORTED, "gemm: geglu with rowvec");
-    // 8-byte vector epilogue when every row start / column quad is 8-byte aligned
-    auto al8 = [](const void* q) { return (((uintptr_t)q) & 7) == 0; };
-    p.vec4 = (d->ldc % 4 == 0 && d->c_bs0 % 4 == 0 && d->c_bs1 % 4 == 0 && al8(d->C) && al8(d->bias) &&
-              al8(d->rowvec) && d->N % 4 == 0 &&
-              (!d->residual || (al8(d->residual) && d->ldr % 4 == 0 && d->r_bs0 % 4 == 0 && d->r_bs1 % 4 == 0)))
-                 ? 1 : 0;
-    // 16-byte stores (two lanes of a pair exchange register quads first) when rows and column octets are 16-byte aligned
-    auto al16 = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-    p.vec8 = (p.vec4 && d->ldc % 8 == 0 && d->c_bs0 % 8 == 0 && d->c_bs1 % 8 == 0 && al16(d->C) && d->N % 8 == 0) ? 1 : 0;
-    p.rvec8 = (p.vec8 && d->residual && al16(d->residual) && d->ldr % 8 == 0 && d->r_bs0 % 8 == 0 && d->r_bs1 % 8 == 0)
-                  ? 1 : 0;
+    fill_vector_widths(d, p);
+    return VSX_OK;
+}
 
-    // tile selection.  cols = rows of B.  The 320-wide tiles need cols % 320 == 0 (no column padding waste) and
-    // enough workgroups to cover the 256 CUs; otherwise fall back to the 128/64 tiles (2 workgroups per CU).
-    const long cols = p.geglu ? 2 * d->N : d->N;
-    auto blocks = [&](long bm, long bn) { return ((d->M + bm - 1) / bm) * ((cols + bn - 1) / bn) * nbatch; };
-    int rc;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool sample = !dry && g_prof.on && !g_prof.paused && g_prof.n < g_prof.max_samples &&
-                        (g_prof.seen++ % g_prof.stride) == 0;
-    if (sample) {
-        if ((long)g_prof.ev->size() < 2 * (g_prof.n + 1)) {
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)
-                return vsx_fail(VSX_E_LAUNCH, "prof: hipEventCreate failed");
-            g_prof.ev->push_back(a);
-            g_prof.ev->push_back(b);
-        }
-        e0 = (*g_prof.ev)[2 * g_prof.n];
-        e1 = (*g_prof.ev)[2 * g_prof.n + 1];
-        (void)hipEventRecord(e0, stream);
-    }
+void set_tile(GemmPlan& plan, int bm, int bn, int waves_m, int waves_n, bool deep = false) {
+    plan.family = GEMM_TILE;
+    plan.BM = bm; plan.BN = bn; plan.WAVES_M = waves_m; plan.WAVES_N = waves_n;
+    plan.deep = deep;
+}
+
+// The workgroup-per-tile kernel of a problem the persistent kernels did not take.  cols = rows of B.  The 320-wide tiles need
+// cols % 320 == 0 (no column padding waste) and enough workgroups to cover the 256 CUs; otherwise fall back to the 128/64 tiles
+// (2 workgroups per CU).
+void plan_tile(const vsx_gemm_desc& d, const GemmParams& p, const int splits, const bool assume_workspace, GemmPlan& plan) {
+    const long nbatch = d.batch0 * d.batch1;
+    const long cols = p.geglu ? 2 * d.N : d.N;
+    auto blocks = [&](long bm, long bn) { return ((d.M + bm - 1) / bm) * ((cols + bn - 1) / bn) * nbatch; };
     const bool wide = (cols % 320 == 0);
-    const int splits = plan_splitk(d, blocks(128, 320), wide && nbatch == 1 && !p.geglu && p.c_mode == 0 && p.vec4);
+    const int64_t split_bytes = (int64_t)splits * d.M * d.N * (int64_t)sizeof(float);
+    plan.forced = force_tile() && (wide || force_tile() >= 4);
+    if (!plan.forced && splits > 1) plan.workspace_bytes = split_bytes;
+    if (plan.forced) {
+        if (force_tile() == 1) set_tile(plan, 128, 320, 4, 2);
+        else if (force_tile() == 2) set_tile(plan, 128, 160, 4, 1, tune_deep());
+        else if (force_tile() == 3) set_tile(plan, 256, 320, 8, 2);
+        else if (force_tile() == 4) set_tile(plan, 128, 128, 2, 2);
+        else if (force_tile() == 5) set_tile(plan, 64, 128, 2, 2);
+        else set_tile(plan, 64, 64, 2, 2);
+    } else if (splits > 1 && (assume_workspace || (d.workspace != nullptr && d.workspace_bytes >= split_bytes))) {
+        const long nk = (d.K + BK - 1) / BK;
+        plan.splits = splits;
+        plan.nk_per = (int)((nk + splits - 1) / splits);
+        set_tile(plan, 128, 320, 4, 2);
+    } else if (wide && blocks(256, 320) >= 240 && (p.a_mode == 1 || p.geglu || p.residual == nullptr)) {
+        // 16 waves (4 per SIMD), 32x160 per wave, 142 FLOP per staged byte: the big-M convolutions, the GEGLU
+        // projections (their erf epilogue overlaps with the other waves' MFMAs) and the residual-free projections.
+        // Measured per shape against the 8- and 4-wave tiles with tools/shape_prof.py (VSX_TUNE_TILE=1|2|3).
+        set_tile(plan, 256, 320, 8, 2);
+    } else if (cols % 160 == 0 && blocks(128, 160) >= 200) {
+        // 4 waves, 32x160 per wave, two workgroups per CU (74 KiB of LDS each): one's epilogue and prologue overlap
+        // with the other's main loop, and its registers leave room to prefetch the residual.  Since the 128-byte-row
+        // slabs it is at least as fast as the 8-wave 128x320 tile on every UNet shape.
+        // at most one workgroup per CU (<= 256 of them): nothing to overlap with, so four ring slots instead of two
+        // (profiles/r04_gemm_small_m_sweep.txt: proj 1280->1280 at M = 4096 35.2 -> 32.9 us, qk 1280->2560 at M = 2048 - 7 %)
+        set_tile(plan, 128, 160, 4, 1, blocks(128, 160) <= 256);
+    } else if (cols % 160 == 0 && blocks(128, 160) >= 176 && !p.geglu && p.c_mode == 0) {
+        set_tile(plan, 128, 160, 4, 1, true);      // qkv 1280->3840 at M = 1024: - 9 %
+    } else if (wide && blocks(128, 320) >= 200) {
+        set_tile(plan, 128, 320, 4, 2);    // 8 waves, 32x160 per wave
+    } else if (blocks(128, 128) >= 512) {
+        set_tile(plan, 128, 128, 2, 2);
+    } else if (blocks(64, 128) >= 512 || (p.geglu && cols >= 128)) {
+        set_tile(plan, 64, 128, 2, 2);
+    } else {
+        set_tile(plan, 64, 64, 2, 2);
+    }
+    if (p.c_mode == 1) plan.deep = false;       // the transposed store has no four-slot instance (launch_tile)
+}
+
+// Which kernel runs this problem: a pure function of the descriptor, the parameters fill_params made of it and the current option
+// values.  `assume_workspace`: plan as if the descriptor carried a workspace large enough for split-K (vsx_gemm_workspace).
+GemmPlan plan_gemm(const vsx_gemm_desc& d, const GemmParams& p, const bool assume_workspace) {
+    GemmPlan plan{};
+    plan.splits = 1;
+    const long nbatch = plan.nbatch = d.batch0 * d.batch1;
+    const long cols = p.geglu ? 2 * d.N : d.N;
+    auto blocks = [&](long bm, long bn) { return ((d.M + bm - 1) / bm) * ((cols + bn - 1) / bn) * nbatch; };
+    const bool wide = (cols % 320 == 0);
+    const int splits = plan_splitk(&d, blocks(128, 320), wide && nbatch == 1 && !p.geglu && p.c_mode == 0 && p.vec4);
     // Persistent ping-pong kernel (gemm_pp.hip): problems with at least ~one 256x320 (or 128x320) tile per CU.
     // VSX_GEMM_PP=0 disables it (A/B measurements against the workgroup-per-tile kernels), 2 forces it whenever the
     // shape is eligible.
@@ -1285,92 +1225,111 @@ static int gemm_impl(const vsx_gemm_desc* d, vsx_stream_t stream_, const bool dr
     // and wins); 3 = the same from 131 072 rows (A/B runs); 4 = 1 + the LayerNorm-folded projections 320 -> 640 / 960 (column slices);
     // 2 = every eligible problem (tests)
     const long ws_opt = gemm_option("gemm_ws");
-    const bool ws_res = d->N == 320 && d->residual != nullptr && d->M >= (ws_opt == 3 ? 131072 : 65536);
-    const bool ws_ln = ws_opt == 4 && d->N > 320 && d->rowscale != nullptr && d->M >= 65536;
-    const bool ws_st = ws_opt == 5 && d->N == 320 && d->rowstats_parts >= 0 && d->rowscale == nullptr && d->residual == nullptr && d->M >= 131072;     // (5: + the residual-free K = N = 320 launches, A/B runs)
+    const bool ws_res = d.N == 320 && d.residual != nullptr && d.M >= (ws_opt == 3 ? 131072 : 65536);
+    const bool ws_ln = ws_opt == 4 && d.N > 320 && d.rowscale != nullptr && d.M >= 65536;
+    const bool ws_st = ws_opt == 5 && d.N == 320 && d.rowstats_parts >= 0 && d.rowscale == nullptr && d.residual == nullptr && d.M >= 131072;     // (5: + the residual-free K = N = 320 launches, A/B runs)
     const bool ws = ws_opt != 0 && pp != 0 && nbatch == 1 && splits <= 1 && !force_tile() && ws_supported(p) && (ws_opt == 2 || ws_res || ws_ln || ws_st);
     // row statistics of the output (vsx.h, ABI 8): only the staged row passes of the persistent kernels produce them
-    const long stat_parts = ws ? (p.rowscale ? 0 : (cols / 320) * ws_waves()) : ((pp256 || pp128) && pp_rowstats_ok(p) ? (cols / 320) * 6 : 0);
-    if (dry) {
-        *parts_out = stat_parts;
-        return VSX_OK;
+    plan.stat_parts = ws ? (p.rowscale ? 0 : (cols / 320) * ws_waves()) : ((pp256 || pp128) && pp_rowstats_ok(p) ? (cols / 320) * 6 : 0);
+    if (d.rowstats != nullptr && !(plan.stat_parts > 0 && d.rowstats_parts == plan.stat_parts)) plan.refused = PLAN_ROWSTATS_PARTS;
+    // the sub-pixel form runs on the persistent kernel only (enough tiles, rows per class a multiple of the tile)
+    if (p.sp_Mc > 0 && !((pp256 && p.sp_Mc % 256 == 0) || (pp128 && p.sp_Mc % 128 == 0)) && !plan.refused)
+        plan.refused = PLAN_SUBPIXEL_OFF_PP;
+    if (ws) plan.family = GEMM_WS;
+    else if (pp256) plan.family = GEMM_PP256;
+    else if (pp128) plan.family = GEMM_PP128;
+    else plan_tile(d, p, splits, assume_workspace, plan);
+    return plan;
+}
+
+// Algorithmic work of one launch for the profiler's roofline (tools/pmc_by_shape.py has the same definition of the bytes): every
+// operand element once.
+void gemm_work(const vsx_gemm_desc& d, const GemmParams& p, double* flop, double* bytes) {
+    const long nbatch = d.batch0 * d.batch1;
+    const long cols = p.geglu ? 2 * d.N : d.N;
+    *flop = 2.0 * (double)d.M * (double)cols * (double)p.K * (double)nbatch;      // (sub-pixel form: the 4 C it multiplies)
+    double a_el = (double)d.M * (double)d.K;
+    if (p.a_mode == 1) {
+        const double nimg = (double)d.M / ((double)p.Ho * (double)p.Wo) / (p.sp_Mc > 0 ? 4.0 : 1.0);
+        const double hin = p.ups ? p.H / 2 : p.H, win = p.ups ? p.W / 2 : p.W;     // (sub-pixel form: p.H, p.W are the source's already)
+        a_el = nimg * hin * win * (double)(p.C1 + p.C2);
     }
-    if (d->rowstats != nullptr) {
-        VSX_REQUIRE(stat_parts > 0 && d->rowstats_parts == stat_parts, VSX_E_UNSUPPORTED,
-                    "gemm: rowstats with %ld parts, but this launch writes %ld (ask vsx_gemm_rowstats_parts first)",
-                    (long)d->rowstats_parts, stat_parts);
-        VSX_REQUIRE(vsx_aligned16(d->rowstats), VSX_E_BADSHAPE, "gemm: rowstats must be 16-byte aligned");
-        p.rowstats = (float*)d->rowstats;
-        p.rowstats_parts = (int)stat_parts;
+    const double w_el = (double)cols * (double)d.K * (p.sp_Mc > 0 ? 4.0 : 1.0);
+    const double c_el = (double)d.M * (double)d.N;
+    *bytes = 2.0 * (double)nbatch * (a_el + w_el + c_el + (d.residual ? c_el : 0.0));
+}
+
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+bool is_tile(const GemmPlan& plan) { return plan.BM == BM && plan.BN == BN && plan.WAVES_M == WAVES_M && plan.WAVES_N == WAVES_N; }
+
+// Launches what the plan names.  No selection logic.
+int run_plan(const GemmPlan& plan, GemmParams& p, hipStream_t stream) {
+    if (plan.family == GEMM_WS) return launch_ws(p, stream);
+    if (plan.family == GEMM_PP256) return launch_pp(p, 256, stream);
+    if (plan.family == GEMM_PP128) return launch_pp(p, 128, stream);
+    const long nbatch = plan.nbatch;
+    const long cols = p.geglu ? 2 * p.N : p.N;
+    if (plan.splits > 1) {
+        p.splitk = plan.splits;
+        p.nk_per = plan.nk_per;
     }
-    if (p.sp_Mc > 0)
-        VSX_REQUIRE((pp256 && p.sp_Mc % 256 == 0) || (pp128 && p.sp_Mc % 128 == 0), VSX_E_UNSUPPORTED,
-                    "gemm: the sub-pixel form runs on the persistent kernel only (enough tiles, rows per class a multiple of the tile)");
-    if (ws) {
-        rc = launch_ws(p, stream);
-    } else if (pp256) {
-        rc = launch_pp(p, 256, stream);
-    } else if (pp128) {
-        rc = launch_pp(p, 128, stream);
-    } else if (force_tile() && (wide || force_tile() >= 4)) {
-        p.ws = (float*)d->workspace;
-        if (force_tile() == 1) rc = launch_tile<128, 320, 4, 2>(p, d->M, cols, nbatch, stream);
-        else if (force_tile() == 2) rc = launch_tile<128, 160, 4, 1>(p, d->M, cols, nbatch, stream, tune_deep());
-        else if (force_tile() == 3) rc = launch_tile<256, 320, 8, 2>(p, d->M, cols, nbatch, stream);
-        else if (force_tile() == 4) rc = launch_tile<128, 128, 2, 2>(p, d->M, cols, nbatch, stream);
-        else if (force_tile() == 5) rc = launch_tile<64, 128, 2, 2>(p, d->M, cols, nbatch, stream);
-        else rc = launch_tile<64, 64, 2, 2>(p, d->M, cols, nbatch, stream);
-    } else if (splits > 1 && d->workspace != nullptr &&
-        d->workspace_bytes >= (int64_t)splits * d->M * d->N * (int64_t)sizeof(float)) {
-        const long nk = (d->K + BK - 1) / BK;
-        p.splitk = splits;
-        p.nk_per = (int)((nk + splits - 1) / splits);
-        p.ws = (float*)d->workspace;
-        rc = launch_tile<128, 320, 4, 2>(p, d->M, cols, nbatch, stream);
-        if (rc == VSX_OK) {
-            const long quads = d->M * (d->N / 4);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, p);
-            rc = vsx_check_launch("vsx_gemm_f16 (split-K reduce)");
-        }
-    } else if (wide && blocks(256, 320) >= 240 && (p.a_mode == 1 || p.geglu || p.residual == nullptr)) {
-        // 16 waves (4 per SIMD), 32x160 per wave, 142 FLOP per staged byte: the big-M convolutions, the GEGLU
-        // projections (their erf epilogue overlaps with the other waves' MFMAs) and the residual-free projections.
-        // Measured per shape against the 8- and 4-wave tiles with tools/shape_prof.py (VSX_TUNE_TILE=1|2|3).
-        rc = launch_tile<256, 320, 8, 2>(p, d->M, cols, nbatch, stream);
-    } else if (cols % 160 == 0 && blocks(128, 160) >= 200) {
-        // 4 waves, 32x160 per wave, two workgroups per CU (74 KiB of LDS each): one's epilogue and prologue overlap
-        // with the other's main loop, and its registers leave room to prefetch the residual.  Since the 128-byte-row
-        // slabs it is at least as fast as the 8-wave 128x320 tile on every UNet shape.
-        // at most one workgroup per CU (<= 256 of them): nothing to overlap with, so four ring slots instead of two
-        // (profiles/r04_gemm_small_m_sweep.txt: proj 1280->1280 at M = 4096 35.2 -> 32.9 us, qk 1280->2560 at M = 2048 - 7 %)
-        rc = launch_tile<128, 160, 4, 1>(p, d->M, cols, nbatch, stream, blocks(128, 160) <= 256);
-    } else if (cols % 160 == 0 && blocks(128, 160) >= 176 && !p.geglu && p.c_mode == 0) {
-        rc = launch_tile<128, 160, 4, 1>(p, d->M, cols, nbatch, stream, true);      // qkv 1280->3840 at M = 1024: - 9 %
-    } else if (wide && blocks(128, 320) >= 200) {
-        rc = launch_tile<128, 320, 4, 2>(p, d->M, cols, nbatch, stream);    // 8 waves, 32x160 per wave
-    } else if (blocks(128, 128) >= 512) {
-        rc = launch_tile<128, 128, 2, 2>(p, d->M, cols, nbatch, stream);
-    } else if (blocks(64, 128) >= 512 || (p.geglu && cols >= 128)) {
-        rc = launch_tile<64, 128, 2, 2>(p, d->M, cols, nbatch, stream);
-    } else {
-        rc = launch_tile<64, 64, 2, 2>(p, d->M, cols, nbatch, stream);
-    }
-    if (sample) {
-        (void)hipEventRecord(e1, stream);
-        g_prof.n += 1;
-        const double flop = 2.0 * (double)d->M * (double)cols * (double)p.K * (double)nbatch;      // (sub-pixel form: the 4 C it multiplies)
-        g_prof.flop += flop;
-        // algorithmic bytes (tools/pmc_by_shape.py has the same definition): every operand element once
-        double a_el = (double)d->M * (double)d->K;
-        if (p.a_mode == 1) {
-            const double nimg = (double)d->M / ((double)p.Ho * (double)p.Wo) / (p.sp_Mc > 0 ? 4.0 : 1.0);
-            const double hin = p.ups ? p.H / 2 : p.H, win = p.ups ? p.W / 2 : p.W;     // (sub-pixel form: p.H, p.W are the source's already)
-            a_el = nimg * hin * win * (double)(p.C1 + p.C2);
-        }
-        const double w_el = (double)cols * (double)d->K * (p.sp_Mc > 0 ? 4.0 : 1.0);
-        const double c_el = (double)d->M * (double)d->N;
-        g_prof.work->push_back(flop);
-        g_prof.work->push_back(2.0 * (double)nbatch * (a_el + w_el + c_el + (d->residual ? c_el : 0.0)));
+    int rc;
+    if (is_tile<256, 320, 8, 2>(plan)) rc = launch_tile<256, 320, 8, 2>(p, p.M, cols, nbatch, stream);
+    else if (is_tile<128, 320, 4, 2>(plan)) rc = launch_tile<128, 320, 4, 2>(p, p.M, cols, nbatch, stream);
+    else if (is_tile<128, 160, 4, 1>(plan)) rc = launch_tile<128, 160, 4, 1>(p, p.M, cols, nbatch, stream, plan.deep);
+    else if (is_tile<128, 128, 2, 2>(plan)) rc = launch_tile<128, 128, 2, 2>(p, p.M, cols, nbatch, stream);
+    else if (is_tile<64, 128, 2, 2>(plan)) rc = launch_tile<64, 128, 2, 2>(p, p.M, cols, nbatch, stream);
+    else if (is_tile<64, 64, 2, 2>(plan)) rc = launch_tile<64, 64, 2, 2>(p, p.M, cols, nbatch, stream);
+    else return vsx_fail(VSX_E_UNSUPPORTED, "gemm: no tile kernel %d x %d", plan.BM, plan.BN);
+    if (plan.splits > 1 && rc == VSX_OK) {
+        const long quads = p.M * (p.N / 4);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, p);
+        rc = vsx_check_launch("vsx_gemm_f16 (split-K reduce)");
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GemmParams p;
+    int rc = fill_params(d, p);
+    if (rc != VSX_OK || d->M == 0) return rc;
+    const GemmPlan plan = plan_gemm(*d, p, false);
+    VSX_REQUIRE(plan.refused != PLAN_ROWSTATS_PARTS, VSX_E_UNSUPPORTED,
+                "gemm: rowstats with %ld parts, but this launch writes %ld (ask vsx_gemm_rowstats_parts first)",
+                (long)d->rowstats_parts, plan.stat_parts);
+    VSX_REQUIRE(plan.refused != PLAN_SUBPIXEL_OFF_PP, VSX_E_UNSUPPORTED,
+                "gemm: the sub-pixel form runs on the persistent kernel only (enough tiles, rows per class a multiple of the tile)");
+    if (d->rowstats != nullptr) {
+        VSX_REQUIRE(vsx_aligned16(d->rowstats), VSX_E_BADSHAPE, "gemm: rowstats must be 16-byte aligned");
+        p.rowstats = (float*)d->rowstats;
+        p.rowstats_parts = (int)plan.stat_parts;
+    }
+    if (plan.forced || plan.splits > 1) p.ws = (float*)d->workspace;
+    const long sample = prof_begin(stream);
+    if (sample == PROF_FAILED) return VSX_E_LAUNCH;
+    rc = run_plan(plan, p, stream);
+    if (sample >= 0) {
+        double flop, bytes;
+        gemm_work(*d, p, &flop, &bytes);
+        prof_end(sample, stream, flop, bytes);
+    }
+    return rc;
+}
+
+// How many row-statistics parts would this launch write?  The same checks and the same plan as the launch itself; 0 whenever the
+// problem does not go to a persistent kernel with an eligible epilogue, and 0 for a descriptor the launch would turn down.
+extern "C" int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d) {
+    GemmParams p;
+    if (!d || d->M <= 0 || fill_params(d, p) != VSX_OK) return 0;
+    return plan_gemm(*d, p, false).stat_parts;
+}
+
+// Bytes of workspace with which this launch takes the split-K path (0: it would not split, whatever it is given).
+extern "C" int64_t vsx_gemm_workspace(const vsx_gemm_desc* d) {
+    GemmParams p;
+    if (!d || d->M <= 0 || fill_params(d, p) != VSX_OK) return 0;
+    return plan_gemm(*d, p, true).workspace_bytes;
 }

@@ -2,6 +2,7 @@
 // parameters and the LDS-DMA helpers.
 #pragma once
 #include "common.h"
+#include "options.h"      // vsxg::gemm_option: the tuning / test switches (the list is in options.cpp)
 
 namespace vsxg {
 
@@ -84,11 +85,6 @@ __device__ __forceinline__ void wait_vmcnt() {
 }
 
 #endif  // __HIPCC__
-
-// Tuning / test switches (vsx_set_option; initial values from the environment): "gemm_pp" (VSX_GEMM_PP: 0 = never use
-// the persistent kernel, 1 = where it is expected to win, 2 = wherever the shape is eligible), "pp_sched"
-// (VSX_PP_SCHED: PP_* bits).
-long gemm_option(const char* name);
 
 // gemm_pp.hip: persistent ping-pong kernel (256x320 / 128x320 tiles).  `bm` selects the row tile.
 bool pp_supported(const GemmParams& p);

@@ -1350,8 +1350,6 @@ bool ws_supported(const GemmParams& p) {
 int ws_waves() { return gemm_option("ws_waves") == 5 ? 5 : 10; }
 
 int launch_ws(GemmParams& p, hipStream_t stream) {
-    static const bool trace = getenv("VSX_WS_TRACE") != nullptr;      // (tests: which launches took this kernel)
-    if (trace) fprintf(stderr, "[vsx] weight-stationary: M=%ld N=%ld res=%d rowvec=%d ln=%d stats=%d\n", p.M, p.N, p.residual != nullptr, p.rowvec != nullptr, p.rowscale != nullptr, p.rowstats != nullptr);
     const int epi = (p.residual || p.rowvec ? EPI_ADD : 0) | (p.rowstats ? EPI_STATS : 0) | (p.rowscale ? EPI_LN : 0);
     const bool w10 = ws_waves() == 10;
 #define VSX_WS_CASE(E) case (E): return w10 ? launch_ws_one<(E), 10>(p, stream) : launch_ws_one<(E), 5>(p, stream);

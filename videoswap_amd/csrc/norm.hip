@@ -2,10 +2,7 @@
 // (+ fused temporal positional encoding) for gfx950.  HBM-bound: 16-byte vector loads/stores,
 // fp32 statistics, deterministic reduction order (no atomics).
 #include "common.h"
-
-namespace vsxg {
-long gemm_option(const char* name);      // gemm.hip: the option table of vsx_set_option
-}
+#include "options.h"
 
 namespace {
 
