@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 12
+#define VSX_ABI_VERSION 13
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -428,6 +428,45 @@ int vsx_dift_cosine_map(const void* feat, int64_t N, int64_t E, int64_t h, int64
 int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
                       int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask,
                       int64_t use_tanh, const float* packed, int64_t packed_floats, float* out, vsx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K14 (ABI 13): multiresolution hash grid in front of the K13 layer stack = IMLP_Hash.forward with pe_type
+ * 'hash_encoding', mlp_type 'origin' (the texture network F_Atlas; implicit_neural_networks.py:117-130, 166-195), and the
+ * grid alone.  The grid is tiny-cuda-nn's HashGrid with Linear interpolation, RESTATED from the published algorithm:
+ * it has not been compared with tinycudann, and this block is the one place that defines it.
+ *   Configuration: n_levels (1 to 32, n_levels * n_features <= 64), n_features = n_features_per_level (2 only),
+ *   log2_hashmap_size (<= 24), base_resolution, per_level_scale; input_dim 2 only; fp32 table.  Anything else:
+ *   VSX_E_UNSUPPORTED, the message names the option.
+ *   Level l:  scale = exp2f(l * log2f(per_level_scale)) * base_resolution - 1 (fp32);  res = (uint32)ceilf(scale) + 1;
+ *   entries = min(round_up(res^2, 8), 2^log2_hashmap_size);  offset = sum of the entries of the levels before it.
+ *   table: [sum of entries][n_features] fp32, level-major, 16-byte aligned, table_floats in all (checked).
+ *   Lookup of x = (x_0, x_1), every x_d within [-2, 2], all integer arithmetic uint32 with wrap-around:
+ *   pos_d = fmaf(scale, x_d, 0.5f);  g_d = (uint32)(int)floorf(pos_d);  w_d = pos_d - floorf(pos_d);  corner c = 0 .. 3 has
+ *   the coordinates g_d + ((c >> d) & 1) and the weight prod_d (bit ? w_d : 1 - w_d); its entry is
+ *   idx = g_0, stride = res;  if stride <= entries: idx += g_1 * stride, stride *= res;  if entries < stride:
+ *   idx = g_0 ^ (g_1 * 2654435761);  idx %= entries.  A feature is the sum over the corners, in corner order, of
+ *   fmaf(weight, table[offset + idx][f], sum); it is output column l * n_features + f.
+ *   Inputs outside [-2, 2], infinities and NaN are not refused: the conversion of pos_d to an integer is then
+ *   unspecified, and so are the values that come out.  Every idx is still reduced modulo entries, so no input reads
+ *   outside the table.
+ *   vsx_hash_mlp_f32 sums a layer that runs one 32 x 32 tile per wave (the output layer; every layer when hidden_dim
+ *   <= 64) in four interleaved partial sums over k, added pairwise; K13 sums every layer in one chain.
+ * vsx_hash_grid_geometry: the level table on the host (any of the five arrays may be NULL; n_levels elements each;
+ *   hashed: 1 where the level takes the hash) -> the table's float count, or a negative VSX_E_*.
+ * vsx_hash_grid_f32: x [N, 2] -> out [N, n_levels * n_features] (8-byte aligned).  Rows past N are not gathered.
+ * vsx_hash_mlp_f32: x [N, 2] -> out [N, output_dim], one launch; output_dim, hidden_dim, mlp_layers, skip_mask, use_tanh,
+ *   packed, packed_floats exactly as K13 with n_levels * n_features encoded columns.
+ * ------------------------------------------------------------------------------------------ */
+int64_t vsx_hash_grid_geometry(int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                               double per_level_scale, float* scale, uint32_t* res, uint32_t* entries, uint32_t* offset,
+                               uint32_t* hashed);
+int vsx_hash_grid_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                      int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                      double per_level_scale, float* out, vsx_stream_t stream);
+int vsx_hash_mlp_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                     int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                     double per_level_scale, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask,
+                     int64_t use_tanh, const float* packed, int64_t packed_floats, float* out, vsx_stream_t stream);
 
 #ifdef __cplusplus
 }

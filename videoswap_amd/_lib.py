@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 12
+VSX_ABI_VERSION = 13
 VSX_E_UNSUPPORTED = -2
 
 
@@ -124,6 +124,11 @@ PROTOTYPES = {
                                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     # fused coordinate MLP of the neural atlas (csrc/atlas.hip)
     'vsx_coord_mlp_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64, c_void_p, c_void_p]),
+    # hash grid of the atlas texture network, alone and in front of the fused MLP (csrc/atlas.hip, K14)
+    'vsx_hash_grid_geometry': (c_int64, [c_int64] * 4 + [c_double] + [c_void_p] * 5),
+    'vsx_hash_grid_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double, c_void_p, c_void_p]),
+    'vsx_hash_mlp_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double] + [c_int64] * 5
+                         + [c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

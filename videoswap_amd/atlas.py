@@ -6,12 +6,19 @@ displacement follows through two finite-difference Jacobians; `F_Alpha` decides 
 The three networks are plain coordinate MLPs (`IMLP_Hash` with mlp_type 'origin'); each is evaluated by ONE launch of the
 fused kernel `ops.coord_mlp` (csrc/atlas.hip), and the propagation is batched over all dragged points and frames: three
 launches whatever the number of points P and frames T (the reference makes about ten tiny calls per point).  Per row the
-arithmetic is that of the reference's per-point calls.  Training an atlas (train_atlas.py, the hash-grid texture
-network `F_Atlas`, the losses) is out of scope.
+arithmetic is that of the reference's per-point calls.
+
+Rendering (the second half of this file) restates the per-frame body of evaluate_model (videoswap/atlas/evaluate.py):
+all five networks of a checkpoint, the texture network `F_Atlas` behind its hash grid (`HashGridMLP`, `ops.hash_mlp`),
+give the reconstruction, the alpha matte, the atlas textures and the PSNR.  The hash grid is restated from the published
+tiny-cuda-nn algorithm and has NOT been compared with tinycudann.  Training an atlas (train_atlas.py, the
+losses) is out of scope.
 """
 import json
+import math
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -218,3 +225,229 @@ def propagate_point_sequence(source_point_path, source_tap_path, target_point_pa
     out = dict(source_tap)
     out['pred_tracks'] = pred_tracks
     return (out, details) if return_details else out
+
+
+# ------------------------------------------------------------------------------------------------
+# Rendering a trained atlas: the hash-grid texture network and evaluate_model's per-frame body
+# ------------------------------------------------------------------------------------------------
+RENDER_MODEL_NAMES = ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha', 'FG_UV_Mapping_Inverse')
+# the encoding_config IMLP_Hash hands to tcnn.Encoding (implicit_neural_networks.py:118-127)
+HASH_GRID = dict(n_levels=16, n_features_per_level=2, log2_hashmap_size=19, base_resolution=16, per_level_scale=1.38)
+
+
+def hash_grid_levels(cfg=HASH_GRID):
+    """The level table of a HashGrid configuration (include/vsx.h K14, restated from the published tiny-cuda-nn algorithm):
+    one dict per level with scale (the fp32 value, as a Python float), res, entries, offset (in entries) and hashed."""
+    f32 = np.float32
+    cap = 1 << int(cfg['log2_hashmap_size'])
+    # fp32 log2f / exp2f as correctly rounded values (numpy's own float32 log2 is an ulp off where the C library's is not)
+    log_scale = f32(math.log2(float(f32(cfg['per_level_scale']))))
+    levels, offset = [], 0
+    for l in range(int(cfg['n_levels'])):
+        scale = f32(f32(2.0 ** float(f32(l) * log_scale)) * f32(cfg['base_resolution']) - f32(1))
+        res = int(math.ceil(float(scale))) + 1
+        entries = min((res * res + 7) // 8 * 8, cap)
+        stride = res                                       # after dimension 0
+        if stride <= entries:
+            stride = (stride * res) & 0xffffffff           # dimension 1, uint32
+        levels.append(dict(scale=float(scale), res=res, entries=entries, offset=offset, hashed=entries < stride))
+        offset += entries
+    return levels
+
+
+def hash_grid_floats(cfg=HASH_GRID):
+    """length of the flat table (`encoder.params`) of a configuration"""
+    return sum(lv['entries'] for lv in hash_grid_levels(cfg)) * int(cfg['n_features_per_level'])
+
+
+class _HashGridParams(nn.Module):
+    """holds `params` so that the state-dict key is `encoder.params`, as tcnn.Encoding's"""
+
+    def __init__(self, floats):
+        super().__init__()
+        self.params = nn.Parameter(torch.empty(floats, dtype=torch.float32).uniform_(-1e-4, 1e-4))    # tcnn's initialisation
+
+
+class HashGridMLP(nn.Module):
+    """`IMLP_Hash` with pe_type 'hash_encoding', mlp_type 'origin' (the texture network F_Atlas): same constructor
+    arguments, same state-dict keys (`encoder.params`: the flat fp32 table; `hidden.<i>.weight` / `hidden.<i>.bias`);
+    `forward` is one launch of `ops.hash_mlp`.  `grid` replaces the reference's fixed encoding_config (tests)."""
+
+    def __init__(self, input_dim, output_dim, hidden_dim=256, pe_type='hash_encoding', pe_dim=10, mlp_type='origin',
+                 skip_layers=(), mlp_layers=8, use_tanh=True, fp16=False, grid=None):
+        super().__init__()
+        if pe_type != 'hash_encoding':
+            raise NotImplementedError(f'HashGridMLP: pe_type {pe_type!r} (CoordMLP implements none / encoding)')
+        if mlp_type != 'origin':
+            raise NotImplementedError(f"HashGridMLP: mlp_type {mlp_type!r} is not implemented, only 'origin' (nn.Linear layers)")
+        if fp16:
+            raise NotImplementedError('HashGridMLP: fp16: true (a half-precision grid table) is not implemented, only fp32')
+        if int(input_dim) != 2:
+            raise NotImplementedError(f'HashGridMLP: input_dim {input_dim} (the hash grid is implemented for 2 only)')
+        self.grid = dict(HASH_GRID if grid is None else grid)
+        if int(self.grid['n_features_per_level']) != 2:
+            raise NotImplementedError(f"HashGridMLP: n_features_per_level {self.grid['n_features_per_level']} (only 2)")
+        self.input_dim, self.output_dim, self.hidden_dim = 2, int(output_dim), int(hidden_dim)
+        self.pe_type, self.pe_dim, self.mlp_type = pe_type, int(pe_dim), mlp_type
+        self.skip_layers, self.mlp_layers, self.use_tanh = [int(i) for i in skip_layers], int(mlp_layers), bool(use_tanh)
+        self.encoding_dimensions = int(self.grid['n_levels']) * int(self.grid['n_features_per_level'])
+        self.encoder = _HashGridParams(hash_grid_floats(self.grid))
+        self.hidden = nn.ModuleList()
+        for i in range(self.mlp_layers):
+            if i == 0:
+                k = self.encoding_dimensions
+            elif i in self.skip_layers:
+                k = self.hidden_dim + self.encoding_dimensions
+            else:
+                k = self.hidden_dim
+            self.hidden.append(nn.Linear(k, self.output_dim if i == self.mlp_layers - 1 else self.hidden_dim, bias=True))
+        self._packed = None
+
+    packed = CoordMLP.packed
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        from . import formats
+        table = state_dict.get('encoder.params') if hasattr(state_dict, 'get') else None
+        if table is not None and table.numel() != self.encoder.params.numel():
+            raise formats.FormatError(
+                f'encoder.params holds {table.numel()} values, the hash grid {self.grid} needs {self.encoder.params.numel()} '
+                f'(the level table is restated from the tiny-cuda-nn paper, not taken from the library: DESIGN.md §11)')
+        if table is not None and table.dtype != torch.float32:
+            state_dict = dict(state_dict, **{'encoder.params': table.to(torch.float32)})
+        return super().load_state_dict(state_dict, *args, **kwargs)
+
+    def forward(self, x):
+        lead = x.shape[:-1]
+        x = x.reshape(-1, self.input_dim).to(torch.float32).contiguous()
+        y = ops.hash_mlp(x, self.encoder.params.detach(), self.grid, self.packed(), self.output_dim, self.hidden_dim,
+                         self.mlp_layers, skip_layers=self.skip_layers, use_tanh=self.use_tanh)
+        return y.reshape(*lead, self.output_dim)
+
+
+def load_atlas_render_models(atlas_config, checkpoint_path, device=None):
+    """All five networks of an atlas checkpoint -> {name: module} (RENDER_MODEL_NAMES); `hash_encoding` entries become
+    HashGridMLP, the others CoordMLP."""
+    from . import formats
+    if isinstance(atlas_config, (str, os.PathLike)):
+        atlas_config = load_atlas_config(atlas_config)
+    ckpt = formats._load(checkpoint_path)
+    models = {}
+    for name in RENDER_MODEL_NAMES:
+        if name not in atlas_config.get('models', {}):
+            raise formats.FormatError(f'atlas config: models.{name} is missing')
+        if not isinstance(ckpt, dict) or name not in ckpt:
+            raise formats.FormatError(f'{checkpoint_path}: no {name!r} state dict')
+        kw = atlas_config['models'][name]
+        try:
+            m = HashGridMLP(**kw) if kw.get('pe_type') == 'hash_encoding' else CoordMLP(**kw)
+            m.load_state_dict(ckpt[name])
+        except NotImplementedError as e:
+            raise NotImplementedError(f'models.{name}: {e}') from e
+        except formats.FormatError as e:
+            raise formats.FormatError(f'{checkpoint_path}: {name}: {e}') from e
+        models[name] = m.to(device) if device is not None else m
+    return models
+
+
+def _pixel_axes(res_x, res_y, number_of_frames, device, tensor_time=False):
+    """normalised coordinate of every column, row and frame, computed on the CPU as the reference does: integer tensors
+    divided in fp32; the time coordinate in Python floats, rounded once to fp32 (evaluate_model: `norm_Tcoord_func(f)`
+    times a tensor of ones), or with `tensor_time` as an integer tensor divided and shifted in fp32, two roundings
+    (get_mapping_area:160).  The two differ by an ulp where f / (T / 2) is inexact."""
+    larger = max(int(res_x), int(res_y))
+    xs = torch.arange(int(res_x)) / (larger / 2) - 1
+    ys = torch.arange(int(res_y)) / (larger / 2) - 1
+    if tensor_time:
+        ts = torch.arange(int(number_of_frames)) / (number_of_frames / 2) - 1
+    else:
+        ts = torch.tensor([f / (number_of_frames / 2) - 1 for f in range(int(number_of_frames))], dtype=torch.float64).to(torch.float32)
+    return xs.to(device), ys.to(device), ts.to(device)
+
+
+def render_atlas(models, res_x, res_y, number_of_frames, frames=None, rows_per_call=1 << 20):
+    """The per-frame body of evaluate_model (evaluate.py:263-298, 406-407) for the frames `frames` (default: all):
+    -> dict(reconstruction [F, H, W, 3], alpha [F, H, W], uv_fg [F, H, W, 2], uv_bg [F, H, W, 2], launches) on the
+    networks' device.  Pixels go through the networks in the reference's row order, `rows_per_call` at a time across
+    frame borders; a chunk costs four launches: FG_UV_Mapping, BG_UV_Mapping, F_Alpha, and ONE F_Atlas launch for the
+    foreground and background queries together."""
+    FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
+    device = next(FG.parameters()).device
+    W, H, T = int(res_x), int(res_y), int(number_of_frames)
+    frames = list(range(T)) if frames is None else [int(f) for f in frames]
+    if any(not 0 <= f < T for f in frames):
+        raise ValueError(f'frames {frames} outside 0 .. {T - 1}')
+    xs, ys, ts = _pixel_axes(W, H, T, device)
+    ts = ts[torch.tensor(frames, dtype=torch.long, device=device)] if frames else ts[:0]
+    total = len(frames) * H * W
+    rgb = torch.empty(total, 3, dtype=torch.float32, device=device)
+    alpha = torch.empty(total, 1, dtype=torch.float32, device=device)
+    uv_fg = torch.empty(total, 2, dtype=torch.float32, device=device)
+    uv_bg = torch.empty(total, 2, dtype=torch.float32, device=device)
+    launches = 0
+    with torch.no_grad():
+        for r0 in range(0, total, int(rows_per_call)):
+            r1 = min(r0 + int(rows_per_call), total)
+            idx = torch.arange(r0, r1, device=device)
+            f, rem = idx // (H * W), idx % (H * W)
+            xyt = torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+            uv1, uv2, a = FG(xyt), BG(xyt), F_Alpha(xyt)
+            both = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0))
+            launches += 4
+            rgb1, rgb2 = (both[:r1 - r0] + 1) * 0.5, (both[r1 - r0:] + 1) * 0.5
+            a = 0.5 * (a + 1.0)
+            a = a * 0.99
+            a = a + 0.001
+            rgb[r0:r1] = rgb1 * a + rgb2 * (1.0 - a)
+            alpha[r0:r1], uv_fg[r0:r1], uv_bg[r0:r1] = a, uv1, uv2
+    n = len(frames)
+    return dict(reconstruction=rgb.view(n, H, W, 3), alpha=alpha.view(n, H, W), uv_fg=uv_fg.view(n, H, W, 2),
+                uv_bg=uv_bg.view(n, H, W, 2), launches=launches)
+
+
+def atlas_psnr(reconstruction, frames):
+    """skimage.metrics.peak_signal_noise_ratio(data_range=1) per frame, as evaluate.py:516-519 uses it, and the mean
+    (:591): [F, H, W, 3] values in [0, 1] -> (float64 [F], float)."""
+    mse = ((reconstruction.double().cpu() - frames.double().cpu()) ** 2).flatten(1).mean(dim=1)
+    psnr = 10 * torch.log10(1.0 / mse)
+    return psnr, float(psnr.mean())
+
+
+def mapping_area(mapping, F_Alpha, res_x, res_y, number_of_frames, uv_shift, masks=None, invert_alpha=False,
+                 alpha_thresh=-0.5, rows_per_call=1 << 20):
+    """get_mapping_area (evaluate.py:143-187) -> (maxx, minx, maxy, miny, edge_size) as floats: the box of
+    `mapping(xyt) * 0.5 + uv_shift` over the pixels of `masks` (bool [T, H, W]; None: every pixel) whose F_Alpha output
+    (negated when `invert_alpha`) exceeds `alpha_thresh`.  With the reference's quirks: both pixel axes are normalised
+    by the larger side, the box starts as (min 1, max -1) and is clamped to [-1, 1], edge_size is the larger extent."""
+    device = next(mapping.parameters()).device
+    W, H, T = int(res_x), int(res_y), int(number_of_frames)
+    xs, ys, ts = _pixel_axes(W, H, T, device, tensor_time=True)
+    if masks is None:
+        rows = torch.arange(T * H * W, device=device)
+    else:
+        rows = torch.nonzero(torch.as_tensor(masks).to(device).reshape(-1), as_tuple=False).reshape(-1)
+    lo = torch.tensor([1.0, 1.0], device=device)
+    hi = torch.tensor([-1.0, -1.0], device=device)
+    with torch.no_grad():
+        for r0 in range(0, rows.numel(), int(rows_per_call)):
+            idx = rows[r0:r0 + int(rows_per_call)]
+            f, rem = idx // (H * W), idx % (H * W)
+            xyt = torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+            uv, a = mapping(xyt), F_Alpha(xyt).reshape(-1)
+            keep = (-a if invert_alpha else a) > alpha_thresh
+            if bool(keep.any()):
+                uv = uv[keep] * 0.5 + uv_shift
+                lo, hi = torch.minimum(lo, uv.min(dim=0).values), torch.maximum(hi, uv.max(dim=0).values)
+    (minx, miny), (maxx, maxy) = lo.clamp(min=-1).tolist(), hi.clamp(max=1).tolist()
+    return maxx, minx, maxy, miny, max(maxx - minx, maxy - miny)
+
+
+def atlas_texture(F_Atlas, resolution, minx, maxx, miny, maxy):
+    """`texture_orig` of get_high_res_texture (evaluate.py:89-105, without the cv2 annotation): F_Atlas on the
+    linspace grid [miny, maxy] x [minx, maxx] -> [resolution, resolution, 3] in [0, 1], one launch."""
+    device = next(F_Atlas.parameters()).device
+    n = int(resolution)
+    indsx = torch.linspace(float(minx), float(maxx), n)
+    indsy = torch.linspace(float(miny), float(maxy), n)
+    uv = torch.stack((indsx.unsqueeze(0).expand(n, n), indsy.unsqueeze(1).expand(n, n)), dim=-1).reshape(-1, 2)
+    with torch.no_grad():
+        return 0.5 * (F_Atlas(uv.to(device)).reshape(n, n, 3) + 1)

@@ -15,6 +15,13 @@
 // Work split of a layer with nft = out_features / 32 feature tiles and 2 row tiles: nft > 2: wave w owns feature tiles
 // w and w + 4, both row tiles (64 accumulator registers); nft <= 2 (hidden 32 / 64 and the output layer, padded to 32
 // features): wave w owns feature tile w / 2, row tile w % 2.
+//
+// K14: the same kernel behind a multiresolution hash grid (tiny-cuda-nn's HashGrid, Linear interpolation, 2-D input, 2
+// features per level: the texture network F_Atlas), and the grid alone.  The kernel is a template on the encoding; the grid
+// instantiation fills `enc` by gathering the four corners of every level straight from the table in global memory (21 MB
+// for the reference's configuration: it is not staged in LDS) and runs the same layer loop.  The definition of the grid
+// (level geometry: hg_geometry; lookup: hg_encode4) is RESTATED from the published algorithm and has not been compared
+// with tinycudann.
 #include <math.h>
 
 #include "common.h"
@@ -38,9 +45,68 @@ struct CoordMlpParams {
     int w_off[CM_MAX_LAYERS], b_off[CM_MAX_LAYERS];   // in floats, multiples of 4
 };
 
+constexpr int HG_MAX_LEVELS = 32;
+constexpr int HG_PASS = 16;          // levels per pass of a workgroup: 4 waves x 4 levels per thread
+
+struct HgLevel {
+    float scale;                     // grid cells per unit, minus the half-cell shift's 1
+    uint32_t res, entries, offset;   // offset: first entry of the level in the table
+    uint32_t hashed;                 // 0: dense index g0 + g1 * res, 1: spatial hash
+};
+
+struct HashGrid {
+    static constexpr bool kHash = true;
+    const float2* table;             // [sum entries][2 features], level-major
+    int n_levels;
+    HgLevel lv[HG_MAX_LEVELS];       // unused levels: entries 1, never read from the table
+};
+
+struct NoGrid {
+    static constexpr bool kHash = false;
+};
+
+// The two features of the levels l0 .. l0 + 3 at (x0, x1): f[j] = sum over the four corners of the cell, in corner order,
+// of weight * table entry.  All index arithmetic is uint32 with wrap-around; every index is reduced modulo the level's
+// entry count, so no coordinate (negative, huge, NaN) can address outside the table.  `ok` false (row past N) or a level
+// past n_levels: nothing is gathered, the features are zero.  The 16 eight-byte loads are issued before the first use.
+__device__ __forceinline__ void hg_encode4(const HashGrid& g, int l0, bool ok, float x0, float x1, float2 (&f)[4]) {
+    float2 v[4][4];
+    float w0[4], w1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int l = l0 + j;
+        const HgLevel lv = g.lv[l & (HG_MAX_LEVELS - 1)];
+        const bool use = ok && l < g.n_levels;
+        const float p0 = fmaf(lv.scale, x0, 0.5f), p1 = fmaf(lv.scale, x1, 0.5f);
+        const float fl0 = floorf(p0), fl1 = floorf(p1);
+        const uint32_t g0 = (uint32_t)(int)fl0, g1 = (uint32_t)(int)fl1;
+        w0[j] = p0 - fl0, w1[j] = p1 - fl1;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint32_t c0 = g0 + (c & 1), c1 = g1 + (c >> 1);
+            uint32_t idx = lv.hashed ? (c0 ^ (c1 * 2654435761u)) : c0 + c1 * lv.res;
+            idx %= lv.entries;
+            v[j][c] = use ? g.table[lv.offset + idx] : float2{0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float w = ((c & 1) ? w0[j] : 1.f - w0[j]) * ((c >> 1) ? w1[j] : 1.f - w1[j]);
+            a = fmaf(w, v[j][c].x, a), b = fmaf(w, v[j][c].y, b);
+        }
+        f[j] = float2{a, b};
+    }
+}
+
 // acc[f][r] += W[tile ft[f]][kb0 .. kb0 + nkb) * lds[.. nkb)  for the wave's NF feature tiles and NR row tiles.
 // wl: the layer's packed weight, KB its k-blocks per feature tile; lds: the k-block 0 of this part, [q][CM_BM] float4.
-template <int NF, int NR>
+// S = 4 (one feature tile, one row tile only: 16 of the 64 accumulator registers are in use): the four MFMAs of a k-block
+// go to four partial sums that are added pairwise at the end, so a summation chain is K / 4 long instead of K and the
+// rounding error of the sum is that of a blocked CPU GEMM; S = 1: one chain over k, in order.
+template <int NF, int NR, int S>
 __device__ __forceinline__ void cm_accumulate(f16v (&acc)[2][2], const float* __restrict__ wl, int KB, int kb0, int nkb,
                                               const f4v* lds, const int (&ft)[2], int rt0, int lane) {
     const f4v* wp[NF];
@@ -51,6 +117,14 @@ __device__ __forceinline__ void cm_accumulate(f16v (&acc)[2][2], const float* __
         wn[f] = wp[f][0];
     }
     const f4v* ap = lds + (lane >> 5) * CM_BM + rt0 * 32 + (lane & 31);
+    static_assert(S == 1 || (S == 4 && NF == 1 && NR == 1), "partial sums: one tile per wave only");
+    f16v part[S > 1 ? S - 1 : 1];
+    if constexpr (S > 1) {
+#pragma unroll
+        for (int q = 0; q < S - 1; ++q)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) part[q][i] = 0.f;
+    }
     for (int kb = 0; kb < nkb; ++kb) {
         f4v wc[NF], a[NR];
 #pragma unroll
@@ -60,51 +134,79 @@ __device__ __forceinline__ void cm_accumulate(f16v (&acc)[2][2], const float* __
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) a[r] = ap[2 * kb * CM_BM + r * 32];
+        if constexpr (S > 1) {
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[0][0], a[0][0], acc[0][0], 0, 0, 0);
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+            for (int s = 1; s < 4; ++s) part[s - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[0][s], a[0][s], part[s - 1], 0, 0, 0);
+        } else {
 #pragma unroll
-            for (int f = 0; f < NF; ++f)
+            for (int s = 0; s < 4; ++s)
 #pragma unroll
-                for (int r = 0; r < NR; ++r)
-                    acc[f][r] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[f][s], a[r][s], acc[f][r], 0, 0, 0);
+                for (int f = 0; f < NF; ++f)
+#pragma unroll
+                    for (int r = 0; r < NR; ++r)
+                        acc[f][r] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[f][s], a[r][s], acc[f][r], 0, 0, 0);
+        }
+    }
+    if constexpr (S > 1) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[0][0][i] = (acc[0][0][i] + part[0][i]) + (part[1][i] + part[2][i]);
     }
 }
 
-template <int NF, int NR>
+template <int NF, int NR, int S = 1>
 __device__ __forceinline__ void cm_layer(f16v (&acc)[2][2], const CoordMlpParams& p, int l, const f4v* act, const f4v* enc,
                                          const int (&ft)[2], int rt0, int lane) {
     const int kbh = l > 0 ? p.hidden / 8 : 0;
     const int kbe = (l == 0 || ((p.skip_mask >> l) & 1)) ? p.encp / 8 : 0;
     const float* wl = p.w + p.w_off[l];
     // torch.cat((x, input), 1): the hidden columns first, then the encoded input
-    if (kbh) cm_accumulate<NF, NR>(acc, wl, kbh + kbe, 0, kbh, act, ft, rt0, lane);
-    if (kbe) cm_accumulate<NF, NR>(acc, wl, kbh + kbe, kbh, kbe, enc, ft, rt0, lane);
+    if (kbh) cm_accumulate<NF, NR, S>(acc, wl, kbh + kbe, 0, kbh, act, ft, rt0, lane);
+    if (kbe) cm_accumulate<NF, NR, S>(acc, wl, kbh + kbe, kbh, kbe, enc, ft, rt0, lane);
 }
 
-__global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpParams p) {
+template <class Grid>
+__global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpParams p, const Grid g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f4v* act = reinterpret_cast<f4v*>(smem);                       // [hidden / 4][CM_BM]
     f4v* enc = act + (p.hidden / 4) * CM_BM;                       // [encp / 4][CM_BM]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long row0 = (long)blockIdx.x * CM_BM;
 
-    // the encoded input (positionalEncoding_vec: for each frequency 2^j pi the sines of all inputs, then the cosines), or
-    // the raw coordinates; rows past N and the padding columns are zero
-    for (int idx = tid; idx < p.encp * CM_BM; idx += CM_THREADS) {
-        const int r = idx & (CM_BM - 1), e = idx / CM_BM;
-        float v = 0.f;
-        if (e < p.enc && row0 + r < p.N) {
-            const float* xr = p.x + (row0 + r) * p.in_dim;
-            if (p.pe_dim == 0) {
-                v = xr[e];
-            } else {
-                const int j = e / (2 * p.in_dim), rem = e - j * 2 * p.in_dim;
-                const bool is_cos = rem >= p.in_dim;
-                const float arg = xr[is_cos ? rem - p.in_dim : rem] * ldexpf(3.14159274101257324f, j);   // fp32 (2^j pi)
-                v = is_cos ? cosf(arg) : sinf(arg);
+    if constexpr (Grid::kHash) {
+        // hash grid: row = tid & 63, wave w takes the levels 4 w .. 4 w + 3 of every pass of 16; the two features of level
+        // l are the columns 2 l, 2 l + 1; rows past N (no gather) and the levels up to encp / 2 are zero
+        const int r = tid & (CM_BM - 1), wl = __builtin_amdgcn_readfirstlane(wave);
+        const bool ok = row0 + r < p.N;
+        const float x0 = ok ? p.x[(row0 + r) * 2] : 0.f, x1 = ok ? p.x[(row0 + r) * 2 + 1] : 0.f;
+        for (int l0 = 0; 2 * l0 < p.encp; l0 += HG_PASS) {
+            float2 f[4];
+            hg_encode4(g, l0 + 4 * wl, ok, x0, x1, f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int e = 2 * (l0 + 4 * wl + j);
+                if (e < p.encp) *reinterpret_cast<float2*>(reinterpret_cast<float*>(enc) + ((e >> 2) * CM_BM + r) * 4 + (e & 3)) = f[j];
             }
         }
-        reinterpret_cast<float*>(enc)[((e >> 2) * CM_BM + r) * 4 + (e & 3)] = v;
+    } else {
+        // the encoded input (positionalEncoding_vec: for each frequency 2^j pi the sines of all inputs, then the cosines), or
+        // the raw coordinates; rows past N and the padding columns are zero
+        for (int idx = tid; idx < p.encp * CM_BM; idx += CM_THREADS) {
+            const int r = idx & (CM_BM - 1), e = idx / CM_BM;
+            float v = 0.f;
+            if (e < p.enc && row0 + r < p.N) {
+                const float* xr = p.x + (row0 + r) * p.in_dim;
+                if (p.pe_dim == 0) {
+                    v = xr[e];
+                } else {
+                    const int j = e / (2 * p.in_dim), rem = e - j * 2 * p.in_dim;
+                    const bool is_cos = rem >= p.in_dim;
+                    const float arg = xr[is_cos ? rem - p.in_dim : rem] * ldexpf(3.14159274101257324f, j);   // fp32 (2^j pi)
+                    v = is_cos ? cosf(arg) : sinf(arg);
+                }
+            }
+            reinterpret_cast<float*>(enc)[((e >> 2) * CM_BM + r) * 4 + (e & 3)] = v;
+        }
     }
     __syncthreads();
 
@@ -131,7 +233,7 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
         else if (nf == 1 && nr == 2)
             cm_layer<1, 2>(acc, p, l, act, enc, ft, rt0, lane);
         else if (nf == 1)
-            cm_layer<1, 1>(acc, p, l, act, enc, ft, rt0, lane);
+            cm_layer<1, 1, Grid::kHash ? 4 : 1>(acc, p, l, act, enc, ft, rt0, lane);   // the output layer, and hidden <= 64
         const float* bias = p.w + p.b_off[l];
         if (last) {
             // features 0 .. out_dim - 1 of row (lane & 31): registers 0 .. 2 of the lanes 0 .. 31
@@ -170,12 +272,30 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
     }
 }
 
+// the grid alone: out[row][2 l + f], the thread mapping of the fused kernel's encoding stage; rows past N neither gather
+// nor store
+__global__ __launch_bounds__(CM_THREADS) void hash_grid_kernel(const float* __restrict__ x, long N, const HashGrid g,
+                                                               float* __restrict__ out) {
+    const int tid = threadIdx.x, r = tid & (CM_BM - 1), wl = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long row = (long)blockIdx.x * CM_BM + r;
+    const bool ok = row < N;
+    const float x0 = ok ? x[row * 2] : 0.f, x1 = ok ? x[row * 2 + 1] : 0.f;
+    for (int l0 = 0; l0 < g.n_levels; l0 += HG_PASS) {
+        float2 f[4];
+        hg_encode4(g, l0 + 4 * wl, ok, x0, x1, f);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int l = l0 + 4 * wl + j;
+            if (ok && l < g.n_levels) *reinterpret_cast<float2*>(out + row * (2 * g.n_levels) + 2 * l) = f[j];
+        }
+    }
+}
+
 inline long cm_round_up(long x, long m) { return (x + m - 1) / m * m; }
 
-// floats of the packed weight buffer (vsx.h), arguments already validated
-long cm_packed_floats(int64_t input_dim, int64_t hidden_dim, int64_t mlp_layers, int64_t pe_type, int64_t pe_dim,
-                      int64_t skip_mask) {
-    const long encp = cm_round_up(pe_type == 1 ? 2 * input_dim * pe_dim : input_dim, 8);
+// floats of the packed weight buffer (vsx.h) of a network with `enc` encoded columns, arguments already validated
+long cm_packed_floats(int64_t enc, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask) {
+    const long encp = cm_round_up(enc, 8);
     long total = 0;
     for (int l = 0; l < mlp_layers; ++l) {
         const long fp = l == mlp_layers - 1 ? 32 : hidden_dim;
@@ -183,6 +303,84 @@ long cm_packed_floats(int64_t input_dim, int64_t hidden_dim, int64_t mlp_layers,
         total += fp * kp + fp;
     }
     return total;
+}
+
+// the layer stack's part of the kernel arguments (p.enc / p.encp set by the caller)
+void cm_fill_layers(CoordMlpParams& p, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask) {
+    long off = 0;
+    for (int l = 0; l < CM_MAX_LAYERS; ++l) {
+        p.w_off[l] = p.b_off[l] = 0;
+        if (l >= mlp_layers) continue;
+        const long fp = l == mlp_layers - 1 ? 32 : hidden_dim;
+        const long kp = (l > 0 ? hidden_dim : 0) + ((l == 0 || ((skip_mask >> l) & 1)) ? p.encp : 0);
+        p.w_off[l] = (int)off, p.b_off[l] = (int)(off + fp * kp);
+        off += fp * kp + fp;
+    }
+}
+
+template <class Grid>
+int cm_launch(const char* what, const CoordMlpParams& p, const Grid& g, vsx_stream_t stream) {
+    const size_t smem = (size_t)(p.hidden + p.encp) * CM_BM * sizeof(float);     // <= 80 KiB: two workgroups per CU
+    static size_t smem_attr = 64 * 1024;
+    if (smem > smem_attr) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&coord_mlp_kernel<Grid>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return vsx_fail(VSX_E_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+        smem_attr = 160 * 1024;
+    }
+    hipLaunchKernelGGL(coord_mlp_kernel<Grid>, dim3((unsigned)((p.N + CM_BM - 1) / CM_BM)), dim3(CM_THREADS), smem,
+                       (hipStream_t)stream, p, g);
+    return vsx_check_launch(what);
+}
+
+// THE definition of the level geometry (tiny-cuda-nn's GridEncoding constructor, restated): per level l
+//   scale = exp2f(l * log2f(per_level_scale)) * base_resolution - 1   (fp32),   res = (uint32)ceilf(scale) + 1,
+//   entries = min(round_up(res^2, 8), 2^log2_hashmap_size),   offset = the running sum of entries,
+// and the index of a corner (g0, g1), uint32 with wrap-around: stride = 1; idx = g0, stride *= res; then, while
+// stride <= entries, idx += g1 * stride, stride *= res; the level is HASHED when entries < stride afterwards.
+// Returns the table's float count, or a negative VSX_E_* (the message names the option).
+int64_t hg_geometry(const char* what, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
+                    int64_t base_resolution, double per_level_scale, HgLevel* lv) {
+    VSX_REQUIRE(n_features == 2, VSX_E_UNSUPPORTED, "%s: n_features_per_level %lld (only 2)", what, (long long)n_features);
+    VSX_REQUIRE(n_levels >= 1 && n_levels <= HG_MAX_LEVELS && n_levels * n_features <= CM_MAX_ENC, VSX_E_UNSUPPORTED,
+                "%s: n_levels %lld (1 to %d, at most %d encoded columns)", what, (long long)n_levels, HG_MAX_LEVELS, CM_MAX_ENC);
+    VSX_REQUIRE(log2_hashmap_size >= 3 && log2_hashmap_size <= 24, VSX_E_UNSUPPORTED, "%s: log2_hashmap_size %lld (3 to 24)",
+                what, (long long)log2_hashmap_size);
+    VSX_REQUIRE(base_resolution >= 1 && base_resolution <= 65536, VSX_E_UNSUPPORTED, "%s: base_resolution %lld (1 to 65536)",
+                what, (long long)base_resolution);
+    VSX_REQUIRE(per_level_scale >= 1.0 && per_level_scale <= 16.0, VSX_E_UNSUPPORTED, "%s: per_level_scale %g (1 to 16)", what,
+                per_level_scale);
+    const uint32_t cap = 1u << log2_hashmap_size;
+    uint64_t offset = 0;
+    for (int l = 0; l < HG_MAX_LEVELS; ++l) {
+        lv[l] = HgLevel{0.f, 1u, 1u, 0u, 0u};
+        if (l >= n_levels) continue;
+        const float scale = exp2f((float)l * log2f((float)per_level_scale)) * (float)base_resolution - 1.0f;
+        // inputs lie within [-2, 2]: 2 * scale + 1.5 must stay far inside int32 for (uint32)(int)floorf(pos)
+        VSX_REQUIRE(scale >= 0.f && scale <= 16777216.f, VSX_E_UNSUPPORTED,
+                    "%s: per_level_scale %g / base_resolution %lld: level %d has %g cells (at most 2^24)", what, per_level_scale,
+                    (long long)base_resolution, l, (double)scale);
+        const uint32_t res = (uint32_t)ceilf(scale) + 1u;
+        const uint64_t dense = ((uint64_t)res * res + 7) / 8 * 8;
+        const uint32_t entries = dense < cap ? (uint32_t)dense : cap;
+        uint32_t stride = res;                                   // after dimension 0 (stride 1 <= entries always)
+        if (stride <= entries) stride *= res;                    // dimension 1, uint32 wrap-around
+        lv[l] = HgLevel{scale, res, entries, (uint32_t)offset, entries < stride ? 1u : 0u};
+        offset += entries;
+    }
+    return (int64_t)offset * n_features;
+}
+
+int hg_fill(const char* what, HashGrid& g, int64_t input_dim, const float* table, int64_t table_floats, int64_t n_levels,
+            int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution, double per_level_scale) {
+    VSX_REQUIRE(input_dim == 2, VSX_E_UNSUPPORTED, "%s: input_dim %lld (the hash grid is implemented for 2 only)", what,
+                (long long)input_dim);
+    const int64_t need = hg_geometry(what, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, g.lv);
+    if (need < 0) return (int)need;
+    VSX_REQUIRE(table_floats == need, VSX_E_BADSHAPE, "%s: the grid table holds %lld floats, this configuration needs %lld", what,
+                (long long)table_floats, (long long)need);
+    g.table = reinterpret_cast<const float2*>(table), g.n_levels = (int)n_levels;
+    return VSX_OK;
 }
 
 }  // namespace
@@ -210,7 +408,7 @@ extern "C" int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, i
     if (N == 0) return VSX_OK;
     VSX_REQUIRE(x && packed && out, VSX_E_BADSHAPE, "coord_mlp: null argument");
     VSX_REQUIRE(vsx_aligned16(packed), VSX_E_BADSHAPE, "coord_mlp: packed weights must be 16-byte aligned");
-    const int64_t need = cm_packed_floats(input_dim, hidden_dim, mlp_layers, pe_type, pe_dim, skip_mask);
+    const int64_t need = cm_packed_floats(enc, hidden_dim, mlp_layers, skip_mask);
     VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "coord_mlp: packed weights hold %lld floats, this network needs %lld",
                 (long long)packed_floats, (long long)need);
 
@@ -220,24 +418,74 @@ extern "C" int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, i
     p.pe_dim = pe_type == 1 ? (int)pe_dim : 0;
     p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
     p.skip_mask = (int)skip_mask, p.use_tanh = use_tanh != 0;
-    long off = 0;
-    for (int l = 0; l < CM_MAX_LAYERS; ++l) {
-        p.w_off[l] = p.b_off[l] = 0;
-        if (l >= mlp_layers) continue;
-        const long fp = l == mlp_layers - 1 ? 32 : hidden_dim;
-        const long kp = (l > 0 ? hidden_dim : 0) + ((l == 0 || ((skip_mask >> l) & 1)) ? p.encp : 0);
-        p.w_off[l] = (int)off, p.b_off[l] = (int)(off + fp * kp);
-        off += fp * kp + fp;
+    cm_fill_layers(p, hidden_dim, mlp_layers, skip_mask);
+    return cm_launch("vsx_coord_mlp_f32", p, NoGrid{}, stream);
+}
+
+extern "C" int64_t vsx_hash_grid_geometry(int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
+                                          int64_t base_resolution, double per_level_scale, float* scale, uint32_t* res,
+                                          uint32_t* entries, uint32_t* offset, uint32_t* hashed) {
+    HgLevel lv[HG_MAX_LEVELS];
+    const int64_t floats = hg_geometry("hash_grid", n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, lv);
+    for (int l = 0; floats >= 0 && l < n_levels; ++l) {
+        if (scale) scale[l] = lv[l].scale;
+        if (res) res[l] = lv[l].res;
+        if (entries) entries[l] = lv[l].entries;
+        if (offset) offset[l] = lv[l].offset;
+        if (hashed) hashed[l] = lv[l].hashed;
     }
-    const size_t smem = (size_t)(p.hidden + p.encp) * CM_BM * sizeof(float);     // <= 80 KiB: two workgroups per CU
-    static size_t smem_attr = 64 * 1024;
-    if (smem > smem_attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&coord_mlp_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return vsx_fail(VSX_E_LAUNCH, "coord_mlp: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        smem_attr = 160 * 1024;
-    }
-    hipLaunchKernelGGL(coord_mlp_kernel, dim3((unsigned)((N + CM_BM - 1) / CM_BM)), dim3(CM_THREADS), smem,
-                       (hipStream_t)stream, p);
-    return vsx_check_launch("vsx_coord_mlp_f32");
+    return floats;
+}
+
+extern "C" int vsx_hash_grid_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                                 int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                                 double per_level_scale, float* out, vsx_stream_t stream) {
+    HashGrid g;
+    const int rc = hg_fill("hash_grid", g, input_dim, table, table_floats, n_levels, n_features, log2_hashmap_size,
+                           base_resolution, per_level_scale);
+    if (rc != VSX_OK) return rc;
+    VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "hash_grid: N = %lld", (long long)N);
+    if (N == 0) return VSX_OK;
+    VSX_REQUIRE(x && table && out, VSX_E_BADSHAPE, "hash_grid: null argument");
+    VSX_REQUIRE(vsx_aligned16(table), VSX_E_BADSHAPE, "hash_grid: the grid table must be 16-byte aligned");
+    VSX_REQUIRE((((uintptr_t)out) & 7) == 0, VSX_E_BADSHAPE, "hash_grid: out must be 8-byte aligned");
+    hipLaunchKernelGGL(hash_grid_kernel, dim3((unsigned)((N + CM_BM - 1) / CM_BM)), dim3(CM_THREADS), 0, (hipStream_t)stream,
+                       x, (long)N, g, out);
+    return vsx_check_launch("vsx_hash_grid_f32");
+}
+
+extern "C" int vsx_hash_mlp_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                                int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                                double per_level_scale, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers,
+                                int64_t skip_mask, int64_t use_tanh, const float* packed, int64_t packed_floats, float* out,
+                                vsx_stream_t stream) {
+    HashGrid g;
+    const int rc = hg_fill("hash_mlp", g, input_dim, table, table_floats, n_levels, n_features, log2_hashmap_size,
+                           base_resolution, per_level_scale);
+    if (rc != VSX_OK) return rc;
+    VSX_REQUIRE(output_dim >= 1 && output_dim <= 3, VSX_E_UNSUPPORTED, "hash_mlp: output_dim %lld (1 to 3)", (long long)output_dim);
+    VSX_REQUIRE(hidden_dim >= 32 && hidden_dim <= 256 && hidden_dim % 32 == 0, VSX_E_UNSUPPORTED,
+                "hash_mlp: hidden_dim %lld (a multiple of 32 up to 256)", (long long)hidden_dim);
+    VSX_REQUIRE(mlp_layers >= 2 && mlp_layers <= CM_MAX_LAYERS, VSX_E_UNSUPPORTED, "hash_mlp: mlp_layers %lld (2 to 8)",
+                (long long)mlp_layers);
+    VSX_REQUIRE(skip_mask >= 0 && (skip_mask & 1) == 0 && (skip_mask >> mlp_layers) == 0, VSX_E_UNSUPPORTED,
+                "hash_mlp: skip_layers must lie in 1 .. mlp_layers - 1 (mask 0x%llx)", (long long)skip_mask);
+    VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "hash_mlp: N = %lld", (long long)N);
+    if (N == 0) return VSX_OK;
+    VSX_REQUIRE(x && table && packed && out, VSX_E_BADSHAPE, "hash_mlp: null argument");
+    VSX_REQUIRE(vsx_aligned16(table), VSX_E_BADSHAPE, "hash_mlp: the grid table must be 16-byte aligned");
+    VSX_REQUIRE(vsx_aligned16(packed), VSX_E_BADSHAPE, "hash_mlp: packed weights must be 16-byte aligned");
+    const long enc = n_levels * n_features;
+    const int64_t need = cm_packed_floats(enc, hidden_dim, mlp_layers, skip_mask);
+    VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "hash_mlp: packed weights hold %lld floats, this network needs %lld",
+                (long long)packed_floats, (long long)need);
+
+    CoordMlpParams p;
+    p.x = x, p.w = packed, p.out = out, p.N = N;
+    p.in_dim = 2, p.out_dim = (int)output_dim, p.hidden = (int)hidden_dim, p.layers = (int)mlp_layers;
+    p.pe_dim = 0;
+    p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
+    p.skip_mask = (int)skip_mask, p.use_tanh = use_tanh != 0;
+    cm_fill_layers(p, hidden_dim, mlp_layers, skip_mask);
+    return cm_launch("vsx_hash_mlp_f32", p, g, stream);
 }

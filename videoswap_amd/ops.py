@@ -814,6 +814,51 @@ def coord_mlp(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type=
     return out
 
 
+def _hash_grid_args(x, table, grid, what):
+    """(input_dim, table_floats, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale) of a call"""
+    _chk(x, 'x', torch.float32)
+    _chk(table, 'table', torch.float32)
+    if x.dim() != 2 or table.dim() != 1:
+        raise _lib.VsxError(f'{what}: x must be [N, input_dim] and the table flat, got {tuple(x.shape)} / {tuple(table.shape)}')
+    return (x.shape[1], _p(table), table.numel(), int(grid['n_levels']), int(grid['n_features_per_level']),
+            int(grid['log2_hashmap_size']), int(grid['base_resolution']), float(grid['per_level_scale']))
+
+
+def hash_grid(x, table, grid):
+    """tiny-cuda-nn's HashGrid (Linear interpolation) as include/vsx.h K14 restates it: x fp32 [N, 2], table fp32 (flat,
+    level-major), grid = the encoding_config dict -> fp32 [N, n_levels * n_features_per_level].  Configurations the kernel
+    does not implement raise NotImplementedError."""
+    d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_grid')
+    out = torch.empty(x.shape[0], cfg[0] * cfg[1], dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    rc = lib.vsx_hash_grid_f32(_p(x), x.shape[0], d, tab, floats, *cfg, _p(out), _stream())
+    if rc == _lib.VSX_E_UNSUPPORTED:
+        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
+    check(rc, 'vsx_hash_grid_f32')
+    return out
+
+
+def hash_mlp(x, table, grid, packed, output_dim, hidden_dim, mlp_layers, skip_layers=(), use_tanh=True):
+    """IMLP_Hash.forward with pe_type 'hash_encoding', mlp_type 'origin' in one launch: `hash_grid` feeding the layer stack
+    of `coord_mlp` (`packed`: atlas.pack_coord_mlp with n_levels * n_features_per_level encoded columns).  x fp32 [N, 2]
+    -> fp32 [N, output_dim]."""
+    d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_mlp')
+    _chk(packed, 'packed', torch.float32)
+    mask = 0
+    for i in skip_layers:
+        if not 0 <= int(i) < 62:
+            raise NotImplementedError(f'hash_mlp: skip_layers {list(skip_layers)}')
+        mask |= 1 << int(i)
+    out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    rc = lib.vsx_hash_mlp_f32(_p(x), x.shape[0], d, tab, floats, *cfg, int(output_dim), int(hidden_dim), int(mlp_layers),
+                              mask, int(bool(use_tanh)), _p(packed), packed.numel(), _p(out), _stream())
+    if rc == _lib.VSX_E_UNSUPPORTED:
+        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
+    check(rc, 'vsx_hash_mlp_f32')
+    return out
+
+
 _options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0'))}
 
 
@@ -1035,7 +1080,8 @@ _ACTIVATIONS = {
 }
 _PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
-          'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp')
+          'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
+          'hash_mlp')
 
 
 def _publish(name):
