@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 13
+#define VSX_ABI_VERSION 14
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -467,6 +467,44 @@ int vsx_hash_mlp_f32(const float* x, int64_t N, int64_t input_dim, const float* 
                      int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
                      double per_level_scale, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask,
                      int64_t use_tanh, const float* packed, int64_t packed_floats, float* out, vsx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K15 (ABI 14): a video edited through its atlas = the texture-reading half of evaluate_model (videoswap/atlas/evaluate.py:
+ * get_colors :64-85 with bilinear_interpolate_numpy :24-45, the "was this texel ever used" masks :373-397 and the
+ * composition :399-404), one launch for N rows (csrc/atlas_edit.hip).  A row is a video pixel that has been
+ * through FG_UV_Mapping, BG_UV_Mapping and F_Alpha.  ALL tensors are fp32 and dense; every product and sum below is ONE fp32
+ * operation (no FMA contraction), in the order written.
+ *   uv_fg, uv_bg [N, 2] (8-byte aligned): the raw network outputs.  alpha [N]: already mapped to 0.001 .. 0.991; it must be
+ *   positive.  Per layer a texture tex [R, R, C] (16-byte aligned; C = 3: the colour, C = 4: an RGBA overlay; R >= 2,
+ *   R * R * C < 2^31; h != w is refused), its box (minx, miny, pixel_size = R / the box's x extent, formed by the caller
+ *   in fp32), with C = 4 the colours base [N, 3] the overlay is laid over, and optionally a mask image [R, R] (h, w given
+ *   and checked against R) that the caller has initialised.  The two layers may differ in R and C.
+ *   Per layer, shift = +0.5 (foreground) / -0.5 (background):
+ *     q = uv * 0.5 + shift;  px = (q.x - minx) * pixel_size;  py = (q.y - miny) * pixel_size   (the x extent's pixel_size for both)
+ *     relevant = floor(px) >= 0 && floor(py) >= 0 && ceil(px) < R && ceil(py) < R   (false for NaN, +-inf and anything far outside)
+ *     x0 = floor(px), x1 = x0 + 1, y0, y1 likewise, each CLIPPED to [0, R - 1];  weights from the clipped corners:
+ *     wa = (x1 - px)(y1 - py), wb = (x1 - px)(py - y0), wc = (px - x0)(y1 - py), wd = (px - x0)(py - y0);
+ *     colour = ((tex[y0, x0] wa + tex[y1, x0] wb) + tex[y0, x1] wc) + tex[y1, x1] wd   (px == R - 1 exactly: x0 == x1, a zero colour
+ *     on a relevant row, as in the reference);  C = 4: colour.rgb = colour.rgb * colour.a + base * (1 - colour.a).
+ *   Outputs, [N, 3] each (4-byte aligned):  fg = relevant_fg ? colour_fg * alpha : 0;  bg = relevant_bg ? colour_bg : 0;
+ *   edit = fg + (relevant_bg ? colour_bg * (1 - alpha) : 0);  relevant [N] uint8: bit 0 foreground, bit 1 background.
+ *   Rows past N are not stored.  A row that is not relevant to a layer reads nothing of that layer's texture or mask.
+ *   Masks: a foreground-relevant row raises the cells (ceil py, ceil px), (floor py, floor px), (floor py, ceil px),
+ *   (ceil py, floor px) of mask_fg to max(old, alpha); a background-relevant row sets those cells of mask_bg to 1.  Both are
+ *   an unsigned integer atomic max on the float's bits: exact and independent of the order of the rows (no float atomic
+ *   anywhere).  DEVIATION: the reference's fancy-indexed `masks1[idx] = np.maximum(masks1[idx], alpha)` keeps the LAST
+ *   writer, not the maximum, when two rows of one 100k-pixel batch share a cell; this computes the true maximum.
+ *   Every texture and mask index is formed from a clamped value; no input value can make the kernel read or write outside
+ *   the buffers it was given.
+ *   Refused (vsx_last_error names the layer): C not 3 or 4 (VSX_E_UNSUPPORTED); a non-square texture, R < 2, R * R * C >= 2^31,
+ *   C = 4 without base, a mask of another size, a null or misaligned pointer (VSX_E_BADSHAPE).
+ * ------------------------------------------------------------------------------------------ */
+int vsx_atlas_edit_f32(const float* uv_fg, const float* uv_bg, const float* alpha, int64_t N,
+                       const float* tex_fg, int64_t fg_h, int64_t fg_w, int64_t fg_c, float fg_minx, float fg_miny,
+                       float fg_pixel_size, const float* base_fg, float* mask_fg, int64_t mask_fg_h, int64_t mask_fg_w,
+                       const float* tex_bg, int64_t bg_h, int64_t bg_w, int64_t bg_c, float bg_minx, float bg_miny,
+                       float bg_pixel_size, const float* base_bg, float* mask_bg, int64_t mask_bg_h, int64_t mask_bg_w,
+                       float* edit, float* fg, float* bg, uint8_t* relevant, vsx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@
 // A workgroup runs as blockDim.x OS threads (blocks one after the other); __syncthreads is a std::barrier over the
 // workgroup, __shfl_xor an exchange through a per-wave scratch array between two wave barriers (all 64 lanes of a wave
 // must call it, as on the hardware), __shared__ is static storage (one workgroup is alive at a time).
+// atomicMax on a 32-bit word is a compare-exchange loop on std::atomic_ref (csrc/atlas_edit.hip's mask updates).
 // Used by tools/cpu_check/check_*.cpp only (with hip_gemm.h for the MFMA / LDS-DMA kernels); never part of a library.
 #pragma once
 #include <math.h>
@@ -11,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <barrier>
 #include <functional>
 #include <memory>
@@ -75,6 +77,18 @@ static inline float __shfl(float v, int src, int width = 64) {
     cpuhip::ctx.wave_bar->arrive_and_wait();
     return r;
 }
+// atomicMax on a 32-bit word of "global" memory (the work-items of a workgroup are OS threads): returns the old value
+static inline unsigned atomicMax(unsigned* address, unsigned value) {
+    std::atomic_ref<unsigned> ref(*address);
+    unsigned old = ref.load(std::memory_order_relaxed);
+    while (old < value && !ref.compare_exchange_weak(old, value, std::memory_order_relaxed)) {
+    }
+    return old;
+}
+// the agent-scope relaxed load in front of it (the compiler's own builtin on the host; the scope is a HIP-mode macro)
+#ifndef __HIP_MEMORY_SCOPE_AGENT
+#define __HIP_MEMORY_SCOPE_AGENT 4
+#endif
 #define __expf(x) expf(x)
 static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
 static inline float __builtin_amdgcn_rcpf(float x) { return 1.0f / x; }

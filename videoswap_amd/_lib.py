@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 13
+VSX_ABI_VERSION = 14
 VSX_E_UNSUPPORTED = -2
 
 
@@ -129,6 +129,10 @@ PROTOTYPES = {
     'vsx_hash_grid_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double, c_void_p, c_void_p]),
     'vsx_hash_mlp_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double] + [c_int64] * 5
                          + [c_void_p, c_int64, c_void_p, c_void_p]),
+    # a video edited through its atlas: texture reads, composition, masks (csrc/atlas_edit.hip, K15)
+    'vsx_atlas_edit_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64]
+                           + ([c_void_p] + [c_int64] * 3 + [c_float] * 3 + [c_void_p, c_void_p, c_int64, c_int64]) * 2
+                           + [c_void_p] * 5),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

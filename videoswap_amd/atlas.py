@@ -11,8 +11,9 @@ arithmetic is that of the reference's per-point calls.
 Rendering (the second half of this file) restates the per-frame body of evaluate_model (videoswap/atlas/evaluate.py):
 all five networks of a checkpoint, the texture network `F_Atlas` behind its hash grid (`HashGridMLP`, `ops.hash_mlp`),
 give the reconstruction, the alpha matte, the atlas textures and the PSNR.  The hash grid is restated from the published
-tiny-cuda-nn algorithm and has NOT been compared with tinycudann.  Training an atlas (train_atlas.py, the
-losses) is out of scope.
+tiny-cuda-nn algorithm and has NOT been compared with tinycudann.  Editing (the third part) restates the
+texture-reading half of evaluate_model (:344-419): the video re-rendered from EDITED texture images through `ops.atlas_edit`
+(csrc/atlas_edit.hip).  Training an atlas (train_atlas.py, the losses) is out of scope.
 """
 import json
 import math
@@ -364,6 +365,13 @@ def _pixel_axes(res_x, res_y, number_of_frames, device, tensor_time=False):
     return xs.to(device), ys.to(device), ts.to(device)
 
 
+def _chunk_xyt(xs, ys, ts, r0, r1, H, W):
+    """rows r0 .. r1 - 1 of the (frame, row, column) pixel order -> [r1 - r0, 3] network inputs (selection only)"""
+    idx = torch.arange(r0, r1, device=xs.device)
+    f, rem = idx // (H * W), idx % (H * W)
+    return torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+
+
 def render_atlas(models, res_x, res_y, number_of_frames, frames=None, rows_per_call=1 << 20):
     """The per-frame body of evaluate_model (evaluate.py:263-298, 406-407) for the frames `frames` (default: all):
     -> dict(reconstruction [F, H, W, 3], alpha [F, H, W], uv_fg [F, H, W, 2], uv_bg [F, H, W, 2], launches) on the
@@ -387,9 +395,7 @@ def render_atlas(models, res_x, res_y, number_of_frames, frames=None, rows_per_c
     with torch.no_grad():
         for r0 in range(0, total, int(rows_per_call)):
             r1 = min(r0 + int(rows_per_call), total)
-            idx = torch.arange(r0, r1, device=device)
-            f, rem = idx // (H * W), idx % (H * W)
-            xyt = torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+            xyt = _chunk_xyt(xs, ys, ts, r0, r1, H, W)
             uv1, uv2, a = FG(xyt), BG(xyt), F_Alpha(xyt)
             both = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0))
             launches += 4
@@ -451,3 +457,105 @@ def atlas_texture(F_Atlas, resolution, minx, maxx, miny, maxy):
     uv = torch.stack((indsx.unsqueeze(0).expand(n, n), indsy.unsqueeze(1).expand(n, n)), dim=-1).reshape(-1, 2)
     with torch.no_grad():
         return 0.5 * (F_Atlas(uv.to(device)).reshape(n, n, 3) + 1)
+
+
+# ------------------------------------------------------------------------------------------------
+# Editing through an atlas: the video re-rendered from edited texture images (evaluate.py:344-419)
+# ------------------------------------------------------------------------------------------------
+def texture_box(minx, miny, edge, resolution):
+    """The box of a texture image as `ops.atlas_edit` takes it: (minx, miny, pixel_size) as Python floats holding fp32
+    values.  pixel_size = resolution / ((minx + edge) - minx) is formed in fp32 TENSORS, as the reference forms it
+    (get_colors, evaluate.py:65, called with `minx, minx + edge_size` of :222-228), not in doubles rounded afterwards:
+    the two differ by an ulp for some boxes, and a position on the edge of a texel follows pixel_size."""
+    mx, my, e = (torch.tensor(float(v), dtype=torch.float32) for v in (minx, miny, edge))
+    pixel_size = int(resolution) / ((mx + e) - mx)
+    return float(mx), float(my), float(pixel_size)
+
+
+def edit_atlas(models, res_x, res_y, number_of_frames, tex_fg, box_fg, tex_bg, box_bg, frames=None, rows_per_call=1 << 20,
+               want_masks=False):
+    """The edit half of evaluate_model's per-frame body (evaluate.py:344-404) for the frames `frames` (default: all):
+    tex_fg / tex_bg [R, R, 3] replace the atlas textures over the boxes box_fg / box_bg (`texture_box`); with 4 channels a
+    texture is an RGBA overlay over the colour F_Atlas gives.  -> dict(edit [F, H, W, 3], edited_fg, edited_bg [F, H, W, 3],
+    relevant uint8 [F, H, W] (bit 0 foreground, bit 1 background), alpha [F, H, W], mask_fg, mask_bg ([R, R], the "was this
+    texel ever used" images of :373-397, None unless `want_masks`), launches).  Row order and chunking are render_atlas's;
+    a chunk costs four launches (FG_UV_Mapping, BG_UV_Mapping, F_Alpha, ops.atlas_edit), five when a texture is RGBA
+    (ONE F_Atlas launch gives both base colours).  mask_fg holds the true maximum of alpha per texel; the reference keeps
+    the last writer among the rows of one batch that share a texel."""
+    FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
+    device = next(FG.parameters()).device
+    W, H, T = int(res_x), int(res_y), int(number_of_frames)
+    frames = list(range(T)) if frames is None else [int(f) for f in frames]
+    if any(not 0 <= f < T for f in frames):
+        raise ValueError(f'frames {frames} outside 0 .. {T - 1}')
+    tex_fg = torch.as_tensor(tex_fg).to(device=device, dtype=torch.float32).contiguous()
+    tex_bg = torch.as_tensor(tex_bg).to(device=device, dtype=torch.float32).contiguous()
+    for name, tex in (('tex_fg', tex_fg), ('tex_bg', tex_bg)):
+        if tex.dim() != 3 or tex.shape[-1] not in (3, 4):
+            raise NotImplementedError(f'edit_atlas: {name} must be [R, R, 3] (a texture) or [R, R, 4] (an RGBA overlay), '
+                                      f'got {tuple(tex.shape)}')
+    overlay = tex_fg.shape[-1] == 4 or tex_bg.shape[-1] == 4
+    masks = None
+    if want_masks:
+        masks = tuple(torch.zeros(t.shape[0], t.shape[1], dtype=torch.float32, device=device) for t in (tex_fg, tex_bg))
+    xs, ys, ts = _pixel_axes(W, H, T, device)
+    ts = ts[torch.tensor(frames, dtype=torch.long, device=device)] if frames else ts[:0]
+    total = len(frames) * H * W
+    edit, fg, bg = (torch.empty(total, 3, dtype=torch.float32, device=device) for _ in range(3))
+    relevant = torch.empty(total, dtype=torch.uint8, device=device)
+    alpha = torch.empty(total, dtype=torch.float32, device=device)
+    launches = 0
+    with torch.no_grad():
+        for r0 in range(0, total, int(rows_per_call)):
+            r1 = min(r0 + int(rows_per_call), total)
+            xyt = _chunk_xyt(xs, ys, ts, r0, r1, H, W)
+            uv1, uv2, a = FG(xyt), BG(xyt), F_Alpha(xyt)
+            a = 0.5 * (a + 1.0)
+            a = a * 0.99
+            a = (a + 0.001).reshape(-1)
+            base1 = base2 = None
+            if overlay:
+                both = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0))
+                base1, base2 = ((both[:r1 - r0] + 1) * 0.5).contiguous(), ((both[r1 - r0:] + 1) * 0.5).contiguous()
+            edit[r0:r1], fg[r0:r1], bg[r0:r1], relevant[r0:r1] = ops.atlas_edit(
+                uv1, uv2, a, tex_fg, box_fg, tex_bg, box_bg, base_fg=base1 if tex_fg.shape[-1] == 4 else None,
+                base_bg=base2 if tex_bg.shape[-1] == 4 else None, masks=masks)
+            alpha[r0:r1] = a
+            launches += 5 if overlay else 4
+    n = len(frames)
+    return dict(edit=edit.view(n, H, W, 3), edited_fg=fg.view(n, H, W, 3), edited_bg=bg.view(n, H, W, 3),
+                relevant=relevant.view(n, H, W), alpha=alpha.view(n, H, W), mask_fg=masks[0] if masks else None,
+                mask_bg=masks[1] if masks else None, launches=launches)
+
+
+def checkerboard(resolution, squares=10):
+    """[resolution, resolution, 3] in {0, 1}: `squares` x `squares` alternating fields, the top-left one white.  Generated,
+    not read: the reference's checkerboard.png is not part of this repository."""
+    n = int(resolution)
+    k = torch.arange(n) * int(squares) // n
+    board = ((k.unsqueeze(0) + k.unsqueeze(1)) % 2 == 0).to(torch.float32)
+    return board.unsqueeze(-1).expand(n, n, 3).contiguous()
+
+
+def checkerboard_videos(models, res_x, res_y, number_of_frames, area_fg, area_bg, frames=None, rows_per_call=1 << 20,
+                        resolution=500, squares=10):
+    """The checkerboard composites of evaluate.py:226-235, 355-361, 415-419: area_fg / area_bg = (minx, miny, edge_size)
+    of the foreground and background mapping areas (`mapping_area`); over each, `atlas_texture` at `resolution` is blended
+    0.7 : 0.3 with a checkerboard and read back through the mapping networks by `edit_atlas`.
+    -> dict(checkerboard_fg = where(relevant, 0.5 (1 - alpha) + fg, 0.5), checkerboard_bg = where(relevant, bg, 0.5),
+    both [F, H, W, 3]; texture_fg, texture_bg: the two blended textures; launches)."""
+    F_Atlas = models['F_Atlas']
+    device = next(F_Atlas.parameters()).device
+    board = checkerboard(resolution, squares).to(device)
+    texs, boxes = [], []
+    for minx, miny, edge in (area_fg, area_bg):
+        tex = atlas_texture(F_Atlas, resolution, minx, minx + edge, miny, miny + edge)
+        texs.append(board * 0.3 + tex * 0.7)
+        boxes.append(texture_box(minx, miny, edge, resolution))
+    out = edit_atlas(models, res_x, res_y, number_of_frames, texs[0], boxes[0], texs[1], boxes[1], frames=frames,
+                     rows_per_call=rows_per_call)
+    rel = out['relevant'].unsqueeze(-1)
+    half = torch.full_like(out['edited_fg'], 0.5)
+    cfg = torch.where((rel & 1) != 0, 0.5 * (1.0 - out['alpha']).unsqueeze(-1) + out['edited_fg'], half)
+    cbg = torch.where((rel & 2) != 0, out['edited_bg'], half)
+    return dict(checkerboard_fg=cfg, checkerboard_bg=cbg, texture_fg=texs[0], texture_bg=texs[1], launches=out['launches'] + 2)

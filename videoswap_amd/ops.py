@@ -859,6 +859,43 @@ def hash_mlp(x, table, grid, packed, output_dim, hidden_dim, mlp_layers, skip_la
     return out
 
 
+def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None, base_bg=None, masks=None):
+    """The texture-reading half of evaluate_model in one launch (include/vsx.h K15): uv_fg, uv_bg fp32 [N, 2] (the mapping
+    networks' outputs), alpha fp32 [N] (0.001 .. 0.991), a texture fp32 [R, R, 3 or 4] and its box (minx, miny, pixel_size:
+    atlas.texture_box) per layer -> (edit [N, 3], fg [N, 3], bg [N, 3], relevant uint8 [N]: bit 0 foreground, bit 1
+    background).  A 4-channel texture is an RGBA overlay over base_fg / base_bg [N, 3].  masks = (mask_fg, mask_bg), fp32
+    [R, R] each or None: updated in place (max with alpha / set to 1 where a relevant row lands).  Channel counts the
+    kernel does not implement raise NotImplementedError, bad buffers VsxError."""
+    _chk(uv_fg, 'uv_fg', torch.float32); _chk(uv_bg, 'uv_bg', torch.float32); _chk(alpha, 'alpha', torch.float32)
+    _chk(tex_fg, 'tex_fg', torch.float32); _chk(tex_bg, 'tex_bg', torch.float32)
+    _chk(base_fg, 'base_fg', torch.float32); _chk(base_bg, 'base_bg', torch.float32)
+    mask_fg, mask_bg = (None, None) if masks is None else masks
+    _chk(mask_fg, 'mask_fg', torch.float32); _chk(mask_bg, 'mask_bg', torch.float32)
+    N = uv_fg.shape[0]
+    if uv_fg.dim() != 2 or uv_fg.shape[1] != 2 or uv_bg.shape != uv_fg.shape or alpha.numel() != N:
+        raise _lib.VsxError(f'atlas_edit: uv_fg / uv_bg must be [N, 2] and alpha [N], got {tuple(uv_fg.shape)} / '
+                            f'{tuple(uv_bg.shape)} / {tuple(alpha.shape)}')
+    layers = []
+    for name, tex, box, base, mask in (('fg', tex_fg, box_fg, base_fg, mask_fg), ('bg', tex_bg, box_bg, base_bg, mask_bg)):
+        if tex.dim() != 3:
+            raise _lib.VsxError(f'atlas_edit: tex_{name} must be [R, R, C], got {tuple(tex.shape)}')
+        if base is not None and tuple(base.shape) != (N, 3):
+            raise _lib.VsxError(f'atlas_edit: base_{name} must be [{N}, 3], got {tuple(base.shape)}')
+        if mask is not None and mask.dim() != 2:
+            raise _lib.VsxError(f'atlas_edit: mask_{name} must be [R, R], got {tuple(mask.shape)}')
+        minx, miny, pixel_size = (float(v) for v in box)
+        layers += [_p(tex), tex.shape[0], tex.shape[1], tex.shape[2], minx, miny, pixel_size, _p(base), _p(mask),
+                   mask.shape[0] if mask is not None else 0, mask.shape[1] if mask is not None else 0]
+    edit, fg, bg = (torch.empty(N, 3, dtype=torch.float32, device=uv_fg.device) for _ in range(3))
+    relevant = torch.empty(N, dtype=torch.uint8, device=uv_fg.device)
+    lib = _lib.load()
+    rc = lib.vsx_atlas_edit_f32(_p(uv_fg), _p(uv_bg), _p(alpha), N, *layers, _p(edit), _p(fg), _p(bg), _p(relevant), _stream())
+    if rc == _lib.VSX_E_UNSUPPORTED:
+        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
+    check(rc, 'vsx_atlas_edit_f32')
+    return edit, fg, bg, relevant
+
+
 _options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0'))}
 
 
@@ -1081,7 +1118,7 @@ _ACTIVATIONS = {
 _PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
-          'hash_mlp')
+          'hash_mlp', 'atlas_edit')
 
 
 def _publish(name):

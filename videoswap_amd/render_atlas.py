@@ -8,7 +8,8 @@ A trained atlas (its YAML and its checkpoint) comes in; `--save_dir` receives
   summary.json                 the two mapping boxes, the launch count and, with `--frame_dir`, the PSNR per frame and its mean.
 `--frame_dir` holds the video frames (sorted by name; resized to res_x x res_y when they differ), `--mask_dir` the
 foreground masks in the same order (the foreground box of the summary then covers masked pixels only, as the reference's).
-The annotated and checkerboard textures, the loss videos and the mp4 writers of the reference are not produced.
+The edited reconstructions and the checkerboard composites are `python -m videoswap_amd.edit_atlas`'s (it takes this
+directory as `--render_dir`); the annotated texture, the loss videos and the mp4 writers of the reference are not produced.
 """
 import argparse
 import json
