@@ -93,6 +93,17 @@ def head_scores(query, key, scale):
     return s.to(H).float().softmax(-1).to(H)
 
 
+def softmax_rows(scores, rows_per_seq=None):
+    """contract of ops.softmax_rows: in place over the last axis of a (row-padded) view; causal: row r is query r % rows_per_seq"""
+    s = scores.float()
+    if rows_per_seq is not None:
+        nk = s.shape[-1]
+        q = (torch.arange(s.numel() // nk) % rows_per_seq).view(*s.shape[:-1], 1)
+        s = s.masked_fill(torch.arange(nk) > q, float('-inf'))
+    scores.copy_(s.softmax(-1).to(H))
+    return scores
+
+
 def attention_pv(probs, vt, kv_div=1):
     nb, heads, nq, nk = probs.shape
     C = vt.shape[1]
@@ -357,7 +368,7 @@ def prof_pause(paused):
     pass
 
 
-_NAMES = ['linear', 'linear_vt', 'conv2d', 'attention_scores', 'head_scores', 'attention_pv', 'attention',
+_NAMES = ['linear', 'linear_vt', 'conv2d', 'attention_scores', 'softmax_rows', 'head_scores', 'attention_pv', 'attention',
           'temporal_attention', 'group_norm', 'layer_norm', 'silu', 'quick_gelu', 'axpy', 'pack_latents',
           'unpack_latents', 'cfg_ddim_step', 'masked_blend', 'adapter_scatter', 'gemm', 'set_option', 'prof_pause',
           'geglu_fwd', 'geglu_bwd', 'silu_bwd', 'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2',

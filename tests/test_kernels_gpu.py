@@ -3,6 +3,10 @@
 Inputs are fp16 (exactly representable in the fp32 reference), so the only differences are the
 accumulation order and the final fp16 rounding: tolerances are a few fp16 ulps of the output scale.
 All calls go through the C ABI (videoswap_amd.ops -> ctypes -> libvsx.so).
+
+The kernels of the training step (csrc/train.hip: GEGLU, SiLU, GroupNorm, LayerNorm and softmax backward, the 2x2 sum pool,
+adapter_gather) and quick_gelu, silu and the two row softmaxes have their parity tests in tests/test_train_kernels_gpu.py:
+each on its own against fp64, with bounds taken from the fp32 ideal on the same inputs.
 """
 import math
 

@@ -288,7 +288,8 @@ __global__ __launch_bounds__(GNB_THREADS) void gnb_apply_kernel(const half_t* __
     }
 }
 
-// LayerNorm backward: one wave per row of C (multiple of 8, <= 2048) elements; 4 rows per workgroup
+// LayerNorm backward: one wave per row of C elements (any C > 0: scalar accesses, each lane strides the row by 64);
+// 4 rows per workgroup
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const half_t* __restrict__ dy, const half_t* __restrict__ x,
                                                      const half_t* __restrict__ gamma, float eps,
                                                      half_t* __restrict__ dx, long M, int C) {

@@ -478,12 +478,30 @@ def attention_scores(q, k, heads, scale, kv_div=1, causal=False, softmax=True):
             gemm(d)
     if not softmax:                  # the raw scaled products (gradient path: dP = dO V^T has the same shape)
         return buf[..., :nk]
-    if causal:
-        check(_lib.load().vsx_softmax_rows_causal(_p(buf), nb * heads * nq, nk, ld, nq, _stream()),
-              'vsx_softmax_rows_causal')
+    return softmax_rows(buf[..., :nk], rows_per_seq=nq if causal else None)
+
+
+def softmax_rows(scores, rows_per_seq=None):
+    """In-place softmax over the last axis of `scores` [.., nk]: a contiguous tensor or the view `buf[..., :nk]` of a buffer
+    whose rows are padded to ld >= nk (the padding is not touched).  rows_per_seq: causal form, row r is query
+    r % rows_per_seq and columns beyond it come out as exact zeros.  Returns `scores`."""
+    _chk_view(scores, 'scores')
+    nk = scores.shape[-1]
+    ld = scores.stride(-2) if scores.dim() >= 2 else nk
+    dense, step = True, ld                  # every leading axis continues the row sequence (axes of size 1 aside)
+    for i in range(scores.dim() - 2, -1, -1):
+        dense = dense and (scores.shape[i] == 1 or scores.stride(i) == step)
+        step *= scores.shape[i]
+    if scores.dim() < 2 or nk == 0 or scores.stride(-1) != 1 or ld < nk or not dense:
+        raise _lib.VsxError(f'softmax_rows: need [.., nk] with unit inner stride and evenly spaced rows, got shape '
+                            f'{tuple(scores.shape)} strides {scores.stride()}')
+    nrows = scores.numel() // nk
+    if rows_per_seq is None:
+        check(_lib.load().vsx_softmax_rows(_p(scores), nrows, nk, ld, _stream()), 'vsx_softmax_rows')
     else:
-        check(_lib.load().vsx_softmax_rows(_p(buf), nb * heads * nq, nk, ld, _stream()), 'vsx_softmax_rows')
-    return buf[..., :nk]
+        check(_lib.load().vsx_softmax_rows_causal(_p(scores), nrows, nk, ld, int(rows_per_seq), _stream()),
+              'vsx_softmax_rows_causal')
+    return scores
 
 
 def head_scores(query, key, scale):
@@ -502,8 +520,7 @@ def head_scores(query, key, scale):
     g.C = probs.data_ptr(); g.ldc = nk; g.c_bs0 = nq * nk
     g.alpha = float(scale)
     gemm(g)
-    check(_lib.load().vsx_softmax_rows(_p(probs), nbh * nq, nk, nk, _stream()), 'vsx_softmax_rows')
-    return probs
+    return softmax_rows(probs)
 
 
 def attention_pv(probs, vt, kv_div=1):
@@ -1007,6 +1024,10 @@ def softmax_bwd(probs, dprobs, scale):
     ld = probs.stride(2)
     if dprobs.shape != probs.shape or dprobs.stride() != probs.stride() or probs.stride(3) != 1:
         raise _lib.VsxError('softmax_bwd: probs and dprobs must share shape and (padded-row) strides')
+    # the kernel walks nb*heads*nq rows of stride ld (the stride of an axis of size 1 is never used)
+    if ld < nk or (heads > 1 and probs.stride(1) != nq * ld) or (nb > 1 and probs.stride(0) != heads * nq * ld):
+        raise _lib.VsxError(f'softmax_bwd: rows must be evenly spaced (strides {probs.stride()} of shape {tuple(probs.shape)}): '
+                            f'pass the whole buf[..., :nk] view, not a slice of its rows')
     _chk_view(probs, 'probs'); _chk_view(dprobs, 'dprobs')
     check(_train_fn('vsx_softmax_bwd')(_p(probs), _p(dprobs), nb * heads * nq, nk, ld, float(scale), _stream()),
           'vsx_softmax_bwd')
@@ -1077,6 +1098,8 @@ def sum_pool2x2(x):
     """[n, 2h, 2w, c] -> [n, h, w, c]: the data gradient of the nearest-2x upsampling folded into a conv's loader."""
     _chk(x, 'x')
     n, h2, w2, c = x.shape
+    if h2 % 2 or w2 % 2:             # the kernel strides the input by 2h and 2w
+        raise _lib.VsxError(f'sum_pool2x2: height and width must be even, got {h2} x {w2}')
     y = torch.empty(n, h2 // 2, w2 // 2, c, dtype=_F16, device=x.device)
     check(_train_fn('vsx_sum_pool2x2')(_p(x), _p(y), n, h2 // 2, w2 // 2, c, _stream()), 'vsx_sum_pool2x2')
     return y
@@ -1089,6 +1112,8 @@ def adapter_gather(tracks, selected, dmap, rate, out_scale=1.0):
     F, P = tracks.shape[:2]
     _, h, w, C = dmap.shape
     dfeat = torch.zeros(P, C, dtype=_F16, device=dmap.device)
+    if P == 0:                       # an empty tensor has no address to hand to the entry point
+        return dfeat
     check(_train_fn('vsx_adapter_gather')(_p(tracks), _p(selected), _p(dmap), _p(dfeat), F, P, C, h, w, float(rate),
                                           float(out_scale), _stream()), 'vsx_adapter_gather')
     return dfeat
@@ -1115,7 +1140,7 @@ _ACTIVATIONS = {
     'unpack_latents': ((0,), ()), 'cfg_ddim_step': ((0, 1, 2), ()), 'masked_blend': ((0, 1), ()),
     'adapter_scatter': ((2,), ()),
 }
-_PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
+_PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'softmax_rows', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
           'hash_mlp', 'atlas_edit')
