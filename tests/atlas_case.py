@@ -90,32 +90,38 @@ class Standin:
 
 
 @contextlib.contextmanager
-def standin():
+def swapped(**entries):
+    """`ops._raw[name] = entry` for the block; the earlier entries come back afterwards"""
     from videoswap_amd import ops
-    s, saved = Standin(), ops._raw.get('coord_mlp')
-    ops._raw['coord_mlp'] = s
+    saved = {k: ops._raw.get(k) for k in entries}
+    ops._raw.update(entries)
     try:
-        yield s
+        yield
     finally:
-        ops._raw['coord_mlp'] = saved
+        ops._raw.update(saved)
 
 
 @contextlib.contextmanager
-def counted():
-    """the real `ops.coord_mlp`, counted"""
+def counted(*names):
+    """the real ops `names` (default: `ops.coord_mlp`), counted together"""
     from videoswap_amd import ops
-    real = ops._raw['coord_mlp']
     box = {'calls': 0}
 
-    def wrapper(*a, **k):
-        box['calls'] += 1
-        return real(*a, **k)
+    def wrap(fn):
+        def wrapper(*a, **k):
+            box['calls'] += 1
+            return fn(*a, **k)
+        return wrapper
 
-    ops._raw['coord_mlp'] = wrapper
-    try:
+    with swapped(**{k: wrap(ops._raw[k]) for k in names or ('coord_mlp',)}):
         yield box
-    finally:
-        ops._raw['coord_mlp'] = real
+
+
+@contextlib.contextmanager
+def standin():
+    s = Standin()
+    with swapped(coord_mlp=s):
+        yield s
 
 
 # ------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import contextlib
 import numpy as np
 import torch
 
+import atlas_case
 import atlas_render_case as arc
 
 F32 = np.float32
@@ -86,9 +87,6 @@ def ref_edit(models, res_x, res_y, number_of_frames, frames, tex_fg, box_fg, tex
     """evaluate_model:263-298 and 344-404 as the reference loops them (per frame, 100k-pixel batches), the networks and the
     texture arithmetic in `dtype` -> dict(edit, edited_fg, edited_bg [F, H, W, 3], relevant [F, H, W], alpha, mask_fg, mask_bg)"""
     np_dtype = np.float64 if dtype == torch.float64 else F32
-    larger = np.maximum(np.int64(res_x), np.int64(res_y))
-    norm_s = lambda v: v / (larger / 2) - 1  # noqa: E731
-    norm_t = lambda v: v / (number_of_frames / 2) - 1  # noqa: E731
     FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
     tex_fg, tex_bg = np.asarray(tex_fg, dtype=F32), np.asarray(tex_bg, dtype=F32)
     n = len(frames)
@@ -97,26 +95,20 @@ def ref_edit(models, res_x, res_y, number_of_frames, frames, tex_fg, box_fg, tex
     alp = np.zeros((n, res_y, res_x), np_dtype)
     masks = (np.zeros(tex_fg.shape[:2], F32), np.zeros(tex_bg.shape[:2], F32))
     with torch.no_grad():
-        for k, f in enumerate(frames):
-            relis_i, reljs_i = torch.where(torch.ones(res_y, res_x) > 0)
-            parts = int(np.ceil(relis_i.shape[0] / 100000))
-            for ii, jj in zip(np.array_split(relis_i.numpy(), parts), np.array_split(reljs_i.numpy(), parts)):
-                relis = norm_s(torch.from_numpy(ii).unsqueeze(1))
-                reljs = norm_s(torch.from_numpy(jj).unsqueeze(1))
-                xyt = torch.cat((reljs, relis, norm_t(f) * torch.ones_like(relis)), dim=1)
-                uv1, uv2 = arc.ref_forward(FG, xyt, dtype), arc.ref_forward(BG, xyt, dtype)
-                alpha = 0.5 * (arc.ref_forward(F_Alpha, xyt, dtype) + 1.0)
-                alpha = alpha * 0.99
-                alpha = alpha + 0.001
-                base1 = base2 = None
-                if tex_fg.shape[2] == 4:
-                    base1 = ((arc.ref_forward(F_Atlas, uv1 * 0.5 + 0.5, dtype) + 1) * 0.5).numpy()
-                if tex_bg.shape[2] == 4:
-                    base2 = ((arc.ref_forward(F_Atlas, uv2 * 0.5 - 0.5, dtype) + 1) * 0.5).numpy()
-                e, a, b, r = edit_rows(uv1.numpy(), uv2.numpy(), alpha.numpy(), tex_fg, box_fg, tex_bg, box_bg, base1, base2,
-                                       masks, dtype=np_dtype)
-                edit[k, ii, jj], efg[k, ii, jj], ebg[k, ii, jj], rel[k, ii, jj] = e, a, b, r
-                alp[k, ii, jj] = alpha[:, 0].numpy()
+        for k, ii, jj, xyt in arc.ref_batches(res_x, res_y, number_of_frames, frames):
+            uv1, uv2 = arc.ref_forward(FG, xyt, dtype), arc.ref_forward(BG, xyt, dtype)
+            alpha = 0.5 * (arc.ref_forward(F_Alpha, xyt, dtype) + 1.0)
+            alpha = alpha * 0.99
+            alpha = alpha + 0.001
+            base1 = base2 = None
+            if tex_fg.shape[2] == 4:
+                base1 = ((arc.ref_forward(F_Atlas, uv1 * 0.5 + 0.5, dtype) + 1) * 0.5).numpy()
+            if tex_bg.shape[2] == 4:
+                base2 = ((arc.ref_forward(F_Atlas, uv2 * 0.5 - 0.5, dtype) + 1) * 0.5).numpy()
+            e, a, b, r = edit_rows(uv1.numpy(), uv2.numpy(), alpha.numpy(), tex_fg, box_fg, tex_bg, box_bg, base1, base2,
+                                   masks, dtype=np_dtype)
+            edit[k, ii, jj], efg[k, ii, jj], ebg[k, ii, jj], rel[k, ii, jj] = e, a, b, r
+            alp[k, ii, jj] = alpha[:, 0].numpy()
     return dict(edit=torch.from_numpy(edit), edited_fg=torch.from_numpy(efg), edited_bg=torch.from_numpy(ebg),
                 relevant=torch.from_numpy(rel), alpha=torch.from_numpy(alp), mask_fg=torch.from_numpy(masks[0]),
                 mask_bg=torch.from_numpy(masks[1]))
@@ -166,27 +158,11 @@ class EditStandin:
 @contextlib.contextmanager
 def standin():
     """the network stand-ins of atlas_render_case plus the edit stand-in: yields (coord_mlp, hash, edit)"""
-    from videoswap_amd import ops
-    e, saved = EditStandin(), ops._raw.get('atlas_edit')
-    ops._raw['atlas_edit'] = e
-    try:
-        with arc.standin() as (c, h):
-            yield c, h, e
-    finally:
-        ops._raw['atlas_edit'] = saved
+    e = EditStandin()
+    with atlas_case.swapped(atlas_edit=e), arc.standin() as (c, h):
+        yield c, h, e
 
 
-@contextlib.contextmanager
 def counted():
     """the real `ops.coord_mlp`, `ops.hash_mlp` and `ops.atlas_edit`, counted together"""
-    from videoswap_amd import ops
-    real = ops._raw['atlas_edit']
-    with arc.counted() as box:
-        def wrapper(*a, **k):
-            box['calls'] += 1
-            return real(*a, **k)
-        ops._raw['atlas_edit'] = wrapper
-        try:
-            yield box
-        finally:
-            ops._raw['atlas_edit'] = real
+    return atlas_case.counted('coord_mlp', 'hash_mlp', 'atlas_edit')

@@ -56,34 +56,41 @@ def ref_forward(m, x, dtype):
     return hash_forward(ws, bs, m.encoder.params, m.grid, x, m.skip_layers, m.use_tanh, dtype)
 
 
-def ref_render(models, res_x, res_y, number_of_frames, frames, dtype):
-    """evaluate_model:263-298 as the reference loops it (per frame, torch.where over the image, 100k-pixel batches),
-    the networks in `dtype` -> reconstruction [F, H, W, 3], alpha [F, H, W], uv_fg, uv_bg"""
+def ref_batches(res_x, res_y, number_of_frames, frames):
+    """the pixels of evaluate_model:263-282 as the reference loops them (per frame, torch.where over the image, 100k-pixel
+    batches): yields (k, ii, jj, xyt) with frames[k] the frame, ii / jj the rows / columns, xyt [n, 3] the fp32 inputs"""
     larger = np.maximum(np.int64(res_x), np.int64(res_y))
     norm_s = lambda v: v / (larger / 2) - 1  # noqa: E731
     norm_t = lambda v: v / (number_of_frames / 2) - 1  # noqa: E731
+    for k, f in enumerate(frames):
+        relis_i, reljs_i = torch.where(torch.ones(res_y, res_x) > 0)
+        parts = int(np.ceil(relis_i.shape[0] / 100000))
+        for ii, jj in zip(np.array_split(relis_i.numpy(), parts), np.array_split(reljs_i.numpy(), parts)):
+            relis = norm_s(torch.from_numpy(ii).unsqueeze(1))
+            reljs = norm_s(torch.from_numpy(jj).unsqueeze(1))
+            xyt = torch.cat((reljs, relis, norm_t(f) * torch.ones_like(relis)), dim=1)
+            assert xyt.dtype == torch.float32
+            yield k, ii, jj, xyt
+
+
+def ref_render(models, res_x, res_y, number_of_frames, frames, dtype):
+    """evaluate_model:263-298 as the reference loops it (`ref_batches`), the networks in `dtype`
+    -> reconstruction [F, H, W, 3], alpha [F, H, W], uv_fg, uv_bg"""
     FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
     rec = torch.zeros(len(frames), res_y, res_x, 3, dtype=dtype)
     alp = torch.zeros(len(frames), res_y, res_x, dtype=dtype)
     uvf, uvb = torch.zeros(len(frames), res_y, res_x, 2, dtype=dtype), torch.zeros(len(frames), res_y, res_x, 2, dtype=dtype)
     with torch.no_grad():
-        for k, f in enumerate(frames):
-            relis_i, reljs_i = torch.where(torch.ones(res_y, res_x) > 0)
-            parts = int(np.ceil(relis_i.shape[0] / 100000))
-            for ii, jj in zip(np.array_split(relis_i.numpy(), parts), np.array_split(reljs_i.numpy(), parts)):
-                relis = norm_s(torch.from_numpy(ii).unsqueeze(1))
-                reljs = norm_s(torch.from_numpy(jj).unsqueeze(1))
-                xyt = torch.cat((reljs, relis, norm_t(f) * torch.ones_like(relis)), dim=1)
-                assert xyt.dtype == torch.float32
-                uv1, uv2 = ref_forward(FG, xyt, dtype), ref_forward(BG, xyt, dtype)
-                rgb1 = (ref_forward(F_Atlas, uv1 * 0.5 + 0.5, dtype) + 1) * 0.5
-                rgb2 = (ref_forward(F_Atlas, uv2 * 0.5 - 0.5, dtype) + 1) * 0.5
-                alpha = 0.5 * (ref_forward(F_Alpha, xyt, dtype) + 1.0)
-                alpha = alpha * 0.99
-                alpha = alpha + 0.001
-                rec[k, ii, jj] = rgb1 * alpha + rgb2 * (1.0 - alpha)
-                alp[k, ii, jj] = alpha[:, 0]
-                uvf[k, ii, jj], uvb[k, ii, jj] = uv1, uv2
+        for k, ii, jj, xyt in ref_batches(res_x, res_y, number_of_frames, frames):
+            uv1, uv2 = ref_forward(FG, xyt, dtype), ref_forward(BG, xyt, dtype)
+            rgb1 = (ref_forward(F_Atlas, uv1 * 0.5 + 0.5, dtype) + 1) * 0.5
+            rgb2 = (ref_forward(F_Atlas, uv2 * 0.5 - 0.5, dtype) + 1) * 0.5
+            alpha = 0.5 * (ref_forward(F_Alpha, xyt, dtype) + 1.0)
+            alpha = alpha * 0.99
+            alpha = alpha + 0.001
+            rec[k, ii, jj] = rgb1 * alpha + rgb2 * (1.0 - alpha)
+            alp[k, ii, jj] = alpha[:, 0]
+            uvf[k, ii, jj], uvb[k, ii, jj] = uv1, uv2
     return dict(reconstruction=rec, alpha=alp, uv_fg=uvf, uv_bg=uvb)
 
 
@@ -103,11 +110,11 @@ def toy_config(hidden=64, real=False):
 def toy_models(config, grid=SMALL_GRID, seed=0, weight_scale=2.0, table_range=0.5, device='cpu'):
     """{name: module} with weights at `weight_scale` x the nn.Linear default initialisation and a grid table uniform in
     [-table_range, table_range] (a texture that varies visibly); grid None: the reference's configuration"""
-    from videoswap_amd.atlas import CoordMLP, HashGridMLP
+    from videoswap_amd.atlas import build_network
     torch.manual_seed(seed)
     models = {}
     for name, kw in config.items():
-        m = HashGridMLP(**kw, grid=grid) if kw['pe_type'] == 'hash_encoding' else CoordMLP(**kw)
+        m = build_network(kw, grid=grid)
         with torch.no_grad():
             for lin in m.hidden:
                 lin.weight.mul_(weight_scale)
@@ -141,33 +148,11 @@ class HashStandin:
 @contextlib.contextmanager
 def standin():
     """both stand-ins: yields (the coord_mlp stand-in, the hash stand-in)"""
-    from videoswap_amd import ops
     h = HashStandin()
-    saved = {k: ops._raw.get(k) for k in ('hash_mlp', 'hash_grid')}
-    ops._raw['hash_mlp'], ops._raw['hash_grid'] = h.hash_mlp, h.hash_grid
-    try:
-        with atlas_case.standin() as c:
-            yield c, h
-    finally:
-        ops._raw.update(saved)
+    with atlas_case.swapped(hash_mlp=h.hash_mlp, hash_grid=h.hash_grid), atlas_case.standin() as c:
+        yield c, h
 
 
-@contextlib.contextmanager
 def counted():
     """the real `ops.coord_mlp` and `ops.hash_mlp`, counted together"""
-    from videoswap_amd import ops
-    real = {k: ops._raw[k] for k in ('coord_mlp', 'hash_mlp')}
-    box = {'calls': 0}
-
-    def wrap(fn):
-        def wrapper(*a, **k):
-            box['calls'] += 1
-            return fn(*a, **k)
-        return wrapper
-
-    for k, fn in real.items():
-        ops._raw[k] = wrap(fn)
-    try:
-        yield box
-    finally:
-        ops._raw.update(real)
+    return atlas_case.counted('coord_mlp', 'hash_mlp')

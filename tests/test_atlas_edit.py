@@ -326,7 +326,7 @@ def test_command_round_trip_render_then_edit(tmp_path):
         args = edit_atlas.parse_args(common + ['--save_dir', save, '--render_dir', rdir, '--frames', '0,2', '--checkerboard', '--write_masks'])
         assert args.frames == [0, 2]
         summary = edit_atlas.run(args, device=torch.device('cpu'))
-        first = atlas.render_atlas(atlas.load_atlas_render_models(cfg_path, ckpt_path), W, H, T, frames=[0, 2])
+        first = atlas.render_atlas(atlas.load_atlas_models(cfg_path, ckpt_path, names=atlas.RENDER_MODEL_NAMES), W, H, T, frames=[0, 2])
     assert sorted(os.listdir(save)) == ['checkerboard_bg', 'checkerboard_fg', 'edit', 'edited_bg', 'edited_fg', 'summary.json',
                                         'texture_edit1.png', 'texture_edit2.png']
     for sub in ('edit', 'edited_fg', 'edited_bg', 'checkerboard_fg', 'checkerboard_bg'):
@@ -350,7 +350,7 @@ def test_command_round_trip_render_then_edit(tmp_path):
         s2 = edit_atlas.run(edit_atlas.parse_args(common + ['--save_dir', save2, '--render_dir', rdir, '--frames', '0,2', '--edit_fg',
                                                             str(tmp_path / 'clear_fg.png'), '--edit_bg', str(tmp_path / 'clear_bg.png')]),
                             device=torch.device('cpu'))
-        out = atlas.edit_atlas(atlas.load_atlas_render_models(cfg_path, ckpt_path), W, H, T, torch.zeros(32, 32, 4),
+        out = atlas.edit_atlas(atlas.load_atlas_models(cfg_path, ckpt_path, names=atlas.RENDER_MODEL_NAMES), W, H, T, torch.zeros(32, 32, 4),
                                atlas.texture_box(0, 0, 1, 32), torch.zeros(32, 32, 4),
                                atlas.texture_box(area['minx'], area['miny'], area['edge_size'], 32), frames=[0, 2])
     assert s2['edit_launches'] == 5 and s2['texture_fg']['channels'] == 4 and sorted(os.listdir(save2)) == ['edit', 'edited_bg', 'edited_fg', 'summary.json']

@@ -296,7 +296,7 @@ def test_command_end_to_end_on_a_synthetic_checkpoint(tmp_path):
                         'models': config}, f)
     torch.save(dict({k: m.state_dict() for k, m in models.items()}, optimizer={'state': {}}, iteration=40000), ckpt_path)
     with standin():
-        loaded = atlas.load_atlas_render_models(cfg_path, ckpt_path)
+        loaded = atlas.load_atlas_models(cfg_path, ckpt_path, names=atlas.RENDER_MODEL_NAMES)
         assert sorted(loaded) == sorted(atlas.RENDER_MODEL_NAMES) and isinstance(loaded['F_Atlas'], atlas.HashGridMLP)
         first = atlas.render_atlas(loaded, W, H, T)
     os.makedirs(tmp_path / 'frames')
@@ -330,6 +330,6 @@ def test_command_end_to_end_on_a_synthetic_checkpoint(tmp_path):
     bad['F_Atlas']['encoder.params'] = torch.zeros(5487024 + 16)
     torch.save(bad, str(tmp_path / 'bad.pth'))
     with pytest.raises(FormatError, match=r'F_Atlas.*5487040.*5487024'):
-        atlas.load_atlas_render_models(cfg_path, str(tmp_path / 'bad.pth'))
+        atlas.load_atlas_models(cfg_path, str(tmp_path / 'bad.pth'), names=atlas.RENDER_MODEL_NAMES)
     with pytest.raises(SystemExit):
         render_atlas.parse_args(['--atlas_config_path', cfg_path, '--atlas_model_path', ckpt_path, '--save_dir', save, '--frames', 'a,b'])

@@ -96,7 +96,7 @@ def main():
         raise SystemExit('atlas_edit_bench needs the GPU: nothing here can be timed on the CPU')
     from videoswap_amd import atlas, ops
     torch.manual_seed(0)
-    nets = {n: (atlas.HashGridMLP(**kw) if kw['pe_type'] == 'hash_encoding' else atlas.CoordMLP(**kw)).cuda() for n, kw in MODELS.items()}
+    nets = {n: atlas.build_network(kw).cuda() for n, kw in MODELS.items()}
     N = RES_X * RES_Y
     tex_fg, tex_bg = torch.rand(R, R, 3, device='cuda'), torch.rand(R, R, 3, device='cuda')
     rgba_fg, rgba_bg = torch.rand(R, R, 4, device='cuda'), torch.rand(R, R, 4, device='cuda')

@@ -90,7 +90,7 @@ def main():
     from videoswap_amd.telemetry import BoardPower
     torch.backends.cuda.matmul.allow_tf32 = False
     torch.manual_seed(0)
-    nets = {n: (atlas.HashGridMLP(**kw) if kw['pe_type'] == 'hash_encoding' else atlas.CoordMLP(**kw)).cuda() for n, kw in MODELS.items()}
+    nets = {n: atlas.build_network(kw).cuda() for n, kw in MODELS.items()}
     chains = {n: (TorchHashChain(m) if isinstance(m, atlas.HashGridMLP) else TorchChain(m)) for n, m in nets.items()}
     fa, fa_chain = nets['F_Atlas'], chains['F_Atlas']
     N = RES_X * RES_Y

@@ -52,25 +52,19 @@ def pack_coord_mlp(weights, biases, hidden_dim, enc_dim, skip_layers=()):
     return torch.cat(parts).contiguous()
 
 
-class CoordMLP(nn.Module):
-    """`IMLP_Hash` (videoswap/atlas/implicit_neural_networks.py:98-195): same constructor arguments, same state-dict keys
-    (`hidden.<i>.weight` / `hidden.<i>.bias`); `forward` is one launch of the fused fp32 kernel.  `pe_type:
-    hash_encoding` and `mlp_type: tcnn` (tinycudann) are not implemented."""
+class _LayerStack(nn.Module):
+    """What the two restatements of `IMLP_Hash` share: the constructor arguments as attributes, the `hidden` list of
+    nn.Linear layers behind `encoding_dimensions` encoded columns (`_build_hidden`, which a subclass calls once its
+    encoding is in place), the packed weights and `forward` around the subclass's `_launch`."""
 
-    def __init__(self, input_dim, output_dim, hidden_dim=256, pe_type='none', pe_dim=10, mlp_type='origin', skip_layers=(),
-                 mlp_layers=8, use_tanh=True, fp16=False):
+    def __init__(self, input_dim, output_dim, hidden_dim, pe_type, pe_dim, mlp_type, skip_layers, mlp_layers, use_tanh):
         super().__init__()
-        if pe_type == 'hash_encoding':
-            raise NotImplementedError("CoordMLP: pe_type 'hash_encoding' (the tinycudann hash grid of F_Atlas) is not "
-                                      "implemented; point propagation does not use it")
-        if pe_type not in ('none', 'encoding'):
-            raise NotImplementedError(f'CoordMLP: pe_type {pe_type!r}')
-        if mlp_type != 'origin':
-            raise NotImplementedError(f"CoordMLP: mlp_type {mlp_type!r} is not implemented, only 'origin' (nn.Linear layers)")
         self.input_dim, self.output_dim, self.hidden_dim = int(input_dim), int(output_dim), int(hidden_dim)
         self.pe_type, self.pe_dim, self.mlp_type = pe_type, int(pe_dim), mlp_type
         self.skip_layers, self.mlp_layers, self.use_tanh = [int(i) for i in skip_layers], int(mlp_layers), bool(use_tanh)
-        self.encoding_dimensions = 2 * self.input_dim * self.pe_dim if pe_type == 'encoding' else self.input_dim
+
+    def _build_hidden(self, encoding_dimensions):
+        self.encoding_dimensions = int(encoding_dimensions)
         self.hidden = nn.ModuleList()
         for i in range(self.mlp_layers):
             if i == 0:
@@ -92,11 +86,31 @@ class CoordMLP(nn.Module):
 
     def forward(self, x):
         lead = x.shape[:-1]
-        x = x.reshape(-1, self.input_dim).to(torch.float32).contiguous()
-        y = ops.coord_mlp(x, self.packed(), self.input_dim, self.output_dim, self.hidden_dim, self.mlp_layers,
-                          pe_type=self.pe_type, pe_dim=self.pe_dim, mlp_type=self.mlp_type, skip_layers=self.skip_layers,
-                          use_tanh=self.use_tanh)
+        y = self._launch(x.reshape(-1, self.input_dim).to(torch.float32).contiguous())
         return y.reshape(*lead, self.output_dim)
+
+
+class CoordMLP(_LayerStack):
+    """`IMLP_Hash` (videoswap/atlas/implicit_neural_networks.py:98-195): same constructor arguments, same state-dict keys
+    (`hidden.<i>.weight` / `hidden.<i>.bias`); `forward` is one launch of the fused fp32 kernel.  `pe_type:
+    hash_encoding` (HashGridMLP implements it) and `mlp_type: tcnn` (tinycudann) are not implemented."""
+
+    def __init__(self, input_dim, output_dim, hidden_dim=256, pe_type='none', pe_dim=10, mlp_type='origin', skip_layers=(),
+                 mlp_layers=8, use_tanh=True, fp16=False):
+        if pe_type == 'hash_encoding':
+            raise NotImplementedError("CoordMLP: pe_type 'hash_encoding' (the tinycudann hash grid of F_Atlas) is not "
+                                      "implemented; point propagation does not use it")
+        if pe_type not in ('none', 'encoding'):
+            raise NotImplementedError(f'CoordMLP: pe_type {pe_type!r}')
+        if mlp_type != 'origin':
+            raise NotImplementedError(f"CoordMLP: mlp_type {mlp_type!r} is not implemented, only 'origin' (nn.Linear layers)")
+        super().__init__(input_dim, output_dim, hidden_dim, pe_type, pe_dim, mlp_type, skip_layers, mlp_layers, use_tanh)
+        self._build_hidden(2 * self.input_dim * self.pe_dim if pe_type == 'encoding' else self.input_dim)
+
+    def _launch(self, x):
+        return ops.coord_mlp(x, self.packed(), self.input_dim, self.output_dim, self.hidden_dim, self.mlp_layers,
+                             pe_type=self.pe_type, pe_dim=self.pe_dim, mlp_type=self.mlp_type, skip_layers=self.skip_layers,
+                             use_tanh=self.use_tanh)
 
 
 def load_atlas_config(path):
@@ -105,27 +119,30 @@ def load_atlas_config(path):
     return load_options(path)
 
 
-def load_atlas_models(atlas_config, checkpoint_path, device=None):
-    """init_atlas_model (propagate_point_displacement.py:59-74) -> (FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha).
-    `atlas_config`: the dict or the path of the YAML.  Every other entry of the checkpoint (BG_UV_Mapping, the hash-grid
-    F_Atlas, optimizer state) is ignored."""
+def load_atlas_models(atlas_config, checkpoint_path, device=None, names=MODEL_NAMES):
+    """init_atlas_model (propagate_point_displacement.py:59-74) -> {name: module} for `names`: the three networks of the
+    propagation by default, all five of a checkpoint with RENDER_MODEL_NAMES (`build_network` picks the class).
+    `atlas_config`: the dict or the path of the YAML.  Every other entry of the checkpoint (optimizer state, networks not
+    named) is ignored."""
     from . import formats
     if isinstance(atlas_config, (str, os.PathLike)):
         atlas_config = load_atlas_config(atlas_config)
     ckpt = formats._load(checkpoint_path)
-    models = []
-    for name in MODEL_NAMES:
+    models = {}
+    for name in names:
         if name not in atlas_config.get('models', {}):
             raise formats.FormatError(f'atlas config: models.{name} is missing')
         if not isinstance(ckpt, dict) or name not in ckpt:
             raise formats.FormatError(f'{checkpoint_path}: no {name!r} state dict')
         try:
-            m = CoordMLP(**atlas_config['models'][name])
+            m = build_network(atlas_config['models'][name])
+            m.load_state_dict(ckpt[name])
         except NotImplementedError as e:
             raise NotImplementedError(f'models.{name}: {e}') from e
-        m.load_state_dict(ckpt[name])
-        models.append(m.to(device) if device is not None else m)
-    return tuple(models)
+        except formats.FormatError as e:
+            raise formats.FormatError(f'{checkpoint_path}: {name}: {e}') from e
+        models[name] = m.to(device) if device is not None else m
+    return models
 
 
 def number_of_frames(atlas_config, num_frames=None):
@@ -269,14 +286,13 @@ class _HashGridParams(nn.Module):
         self.params = nn.Parameter(torch.empty(floats, dtype=torch.float32).uniform_(-1e-4, 1e-4))    # tcnn's initialisation
 
 
-class HashGridMLP(nn.Module):
+class HashGridMLP(_LayerStack):
     """`IMLP_Hash` with pe_type 'hash_encoding', mlp_type 'origin' (the texture network F_Atlas): same constructor
     arguments, same state-dict keys (`encoder.params`: the flat fp32 table; `hidden.<i>.weight` / `hidden.<i>.bias`);
     `forward` is one launch of `ops.hash_mlp`.  `grid` replaces the reference's fixed encoding_config (tests)."""
 
     def __init__(self, input_dim, output_dim, hidden_dim=256, pe_type='hash_encoding', pe_dim=10, mlp_type='origin',
                  skip_layers=(), mlp_layers=8, use_tanh=True, fp16=False, grid=None):
-        super().__init__()
         if pe_type != 'hash_encoding':
             raise NotImplementedError(f'HashGridMLP: pe_type {pe_type!r} (CoordMLP implements none / encoding)')
         if mlp_type != 'origin':
@@ -285,26 +301,13 @@ class HashGridMLP(nn.Module):
             raise NotImplementedError('HashGridMLP: fp16: true (a half-precision grid table) is not implemented, only fp32')
         if int(input_dim) != 2:
             raise NotImplementedError(f'HashGridMLP: input_dim {input_dim} (the hash grid is implemented for 2 only)')
-        self.grid = dict(HASH_GRID if grid is None else grid)
-        if int(self.grid['n_features_per_level']) != 2:
-            raise NotImplementedError(f"HashGridMLP: n_features_per_level {self.grid['n_features_per_level']} (only 2)")
-        self.input_dim, self.output_dim, self.hidden_dim = 2, int(output_dim), int(hidden_dim)
-        self.pe_type, self.pe_dim, self.mlp_type = pe_type, int(pe_dim), mlp_type
-        self.skip_layers, self.mlp_layers, self.use_tanh = [int(i) for i in skip_layers], int(mlp_layers), bool(use_tanh)
-        self.encoding_dimensions = int(self.grid['n_levels']) * int(self.grid['n_features_per_level'])
-        self.encoder = _HashGridParams(hash_grid_floats(self.grid))
-        self.hidden = nn.ModuleList()
-        for i in range(self.mlp_layers):
-            if i == 0:
-                k = self.encoding_dimensions
-            elif i in self.skip_layers:
-                k = self.hidden_dim + self.encoding_dimensions
-            else:
-                k = self.hidden_dim
-            self.hidden.append(nn.Linear(k, self.output_dim if i == self.mlp_layers - 1 else self.hidden_dim, bias=True))
-        self._packed = None
-
-    packed = CoordMLP.packed
+        grid = dict(HASH_GRID if grid is None else grid)
+        if int(grid['n_features_per_level']) != 2:
+            raise NotImplementedError(f"HashGridMLP: n_features_per_level {grid['n_features_per_level']} (only 2)")
+        super().__init__(input_dim, output_dim, hidden_dim, pe_type, pe_dim, mlp_type, skip_layers, mlp_layers, use_tanh)
+        self.grid = grid
+        self.encoder = _HashGridParams(hash_grid_floats(grid))           # before the layers: its place in the state dict
+        self._build_hidden(int(grid['n_levels']) * int(grid['n_features_per_level']))
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         from . import formats
@@ -317,37 +320,15 @@ class HashGridMLP(nn.Module):
             state_dict = dict(state_dict, **{'encoder.params': table.to(torch.float32)})
         return super().load_state_dict(state_dict, *args, **kwargs)
 
-    def forward(self, x):
-        lead = x.shape[:-1]
-        x = x.reshape(-1, self.input_dim).to(torch.float32).contiguous()
-        y = ops.hash_mlp(x, self.encoder.params.detach(), self.grid, self.packed(), self.output_dim, self.hidden_dim,
-                         self.mlp_layers, skip_layers=self.skip_layers, use_tanh=self.use_tanh)
-        return y.reshape(*lead, self.output_dim)
+    def _launch(self, x):
+        return ops.hash_mlp(x, self.encoder.params.detach(), self.grid, self.packed(), self.output_dim, self.hidden_dim,
+                            self.mlp_layers, skip_layers=self.skip_layers, use_tanh=self.use_tanh)
 
 
-def load_atlas_render_models(atlas_config, checkpoint_path, device=None):
-    """All five networks of an atlas checkpoint -> {name: module} (RENDER_MODEL_NAMES); `hash_encoding` entries become
-    HashGridMLP, the others CoordMLP."""
-    from . import formats
-    if isinstance(atlas_config, (str, os.PathLike)):
-        atlas_config = load_atlas_config(atlas_config)
-    ckpt = formats._load(checkpoint_path)
-    models = {}
-    for name in RENDER_MODEL_NAMES:
-        if name not in atlas_config.get('models', {}):
-            raise formats.FormatError(f'atlas config: models.{name} is missing')
-        if not isinstance(ckpt, dict) or name not in ckpt:
-            raise formats.FormatError(f'{checkpoint_path}: no {name!r} state dict')
-        kw = atlas_config['models'][name]
-        try:
-            m = HashGridMLP(**kw) if kw.get('pe_type') == 'hash_encoding' else CoordMLP(**kw)
-            m.load_state_dict(ckpt[name])
-        except NotImplementedError as e:
-            raise NotImplementedError(f'models.{name}: {e}') from e
-        except formats.FormatError as e:
-            raise formats.FormatError(f'{checkpoint_path}: {name}: {e}') from e
-        models[name] = m.to(device) if device is not None else m
-    return models
+def build_network(kw, grid=None):
+    """models.<name> of an atlas YAML -> the module: `hash_encoding` entries become HashGridMLP (over `grid`, default the
+    reference's HASH_GRID), the others CoordMLP."""
+    return HashGridMLP(**kw, grid=grid) if kw.get('pe_type') == 'hash_encoding' else CoordMLP(**kw)
 
 
 def _pixel_axes(res_x, res_y, number_of_frames, device, tensor_time=False):
@@ -365,11 +346,44 @@ def _pixel_axes(res_x, res_y, number_of_frames, device, tensor_time=False):
     return xs.to(device), ys.to(device), ts.to(device)
 
 
-def _chunk_xyt(xs, ys, ts, r0, r1, H, W):
-    """rows r0 .. r1 - 1 of the (frame, row, column) pixel order -> [r1 - r0, 3] network inputs (selection only)"""
-    idx = torch.arange(r0, r1, device=xs.device)
+def _select_xyt(xs, ys, ts, idx, H, W):
+    """rows `idx` of the (frame, row, column) pixel order -> [len(idx), 3] network inputs (selection only)"""
     f, rem = idx // (H * W), idx % (H * W)
     return torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+
+
+def _pixel_chunks(res_x, res_y, number_of_frames, frames, rows_per_call, device):
+    """The pixel loop of render_atlas and edit_atlas -> (n, chunks): the number of frames in `frames` (None: all; checked
+    here, before anything runs) and an iterator of (r0, r1, xyt) over the n H W pixels in the reference's row order,
+    `rows_per_call` at a time across frame borders."""
+    W, H, T = int(res_x), int(res_y), int(number_of_frames)
+    frames = list(range(T)) if frames is None else [int(f) for f in frames]
+    if any(not 0 <= f < T for f in frames):
+        raise ValueError(f'frames {frames} outside 0 .. {T - 1}')
+    xs, ys, ts = _pixel_axes(W, H, T, device)
+    ts = ts[torch.tensor(frames, dtype=torch.long, device=device)] if frames else ts[:0]
+    total, step = len(frames) * H * W, int(rows_per_call)
+
+    def chunks():
+        for r0 in range(0, total, step):
+            r1 = min(r0 + step, total)
+            yield r0, r1, _select_xyt(xs, ys, ts, torch.arange(r0, r1, device=device), H, W)
+    return len(frames), chunks()
+
+
+def _mappings_and_alpha(models, xyt):
+    """three launches -> (uv_fg [n, 2], uv_bg [n, 2], alpha [n, 1] in 0.001 .. 0.991: evaluate.py:283-285, its three steps)"""
+    uv1, uv2, a = models['FG_UV_Mapping'](xyt), models['BG_UV_Mapping'](xyt), models['F_Alpha'](xyt)
+    a = 0.5 * (a + 1.0)
+    a = a * 0.99
+    a = a + 0.001
+    return uv1, uv2, a
+
+
+def _atlas_colours(F_Atlas, uv1, uv2):
+    """ONE F_Atlas launch for the foreground and the background queries together -> (rgb_fg, rgb_bg) [n, 3] in [0, 1]"""
+    both, n = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0)), uv1.shape[0]
+    return (both[:n] + 1) * 0.5, (both[n:] + 1) * 0.5
 
 
 def render_atlas(models, res_x, res_y, number_of_frames, frames=None, rows_per_call=1 << 20):
@@ -378,34 +392,18 @@ def render_atlas(models, res_x, res_y, number_of_frames, frames=None, rows_per_c
     networks' device.  Pixels go through the networks in the reference's row order, `rows_per_call` at a time across
     frame borders; a chunk costs four launches: FG_UV_Mapping, BG_UV_Mapping, F_Alpha, and ONE F_Atlas launch for the
     foreground and background queries together."""
-    FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
-    device = next(FG.parameters()).device
-    W, H, T = int(res_x), int(res_y), int(number_of_frames)
-    frames = list(range(T)) if frames is None else [int(f) for f in frames]
-    if any(not 0 <= f < T for f in frames):
-        raise ValueError(f'frames {frames} outside 0 .. {T - 1}')
-    xs, ys, ts = _pixel_axes(W, H, T, device)
-    ts = ts[torch.tensor(frames, dtype=torch.long, device=device)] if frames else ts[:0]
-    total = len(frames) * H * W
-    rgb = torch.empty(total, 3, dtype=torch.float32, device=device)
-    alpha = torch.empty(total, 1, dtype=torch.float32, device=device)
-    uv_fg = torch.empty(total, 2, dtype=torch.float32, device=device)
-    uv_bg = torch.empty(total, 2, dtype=torch.float32, device=device)
+    device = next(models['FG_UV_Mapping'].parameters()).device
+    W, H = int(res_x), int(res_y)
+    n, chunks = _pixel_chunks(W, H, number_of_frames, frames, rows_per_call, device)
+    rgb, alpha, uv_fg, uv_bg = (torch.empty(n * H * W, c, dtype=torch.float32, device=device) for c in (3, 1, 2, 2))
     launches = 0
     with torch.no_grad():
-        for r0 in range(0, total, int(rows_per_call)):
-            r1 = min(r0 + int(rows_per_call), total)
-            xyt = _chunk_xyt(xs, ys, ts, r0, r1, H, W)
-            uv1, uv2, a = FG(xyt), BG(xyt), F_Alpha(xyt)
-            both = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0))
+        for r0, r1, xyt in chunks:
+            uv1, uv2, a = _mappings_and_alpha(models, xyt)
+            rgb1, rgb2 = _atlas_colours(models['F_Atlas'], uv1, uv2)
             launches += 4
-            rgb1, rgb2 = (both[:r1 - r0] + 1) * 0.5, (both[r1 - r0:] + 1) * 0.5
-            a = 0.5 * (a + 1.0)
-            a = a * 0.99
-            a = a + 0.001
             rgb[r0:r1] = rgb1 * a + rgb2 * (1.0 - a)
             alpha[r0:r1], uv_fg[r0:r1], uv_bg[r0:r1] = a, uv1, uv2
-    n = len(frames)
     return dict(reconstruction=rgb.view(n, H, W, 3), alpha=alpha.view(n, H, W), uv_fg=uv_fg.view(n, H, W, 2),
                 uv_bg=uv_bg.view(n, H, W, 2), launches=launches)
 
@@ -435,9 +433,7 @@ def mapping_area(mapping, F_Alpha, res_x, res_y, number_of_frames, uv_shift, mas
     hi = torch.tensor([-1.0, -1.0], device=device)
     with torch.no_grad():
         for r0 in range(0, rows.numel(), int(rows_per_call)):
-            idx = rows[r0:r0 + int(rows_per_call)]
-            f, rem = idx // (H * W), idx % (H * W)
-            xyt = torch.stack((xs[rem % W], ys[rem // W], ts[f]), dim=1)
+            xyt = _select_xyt(xs, ys, ts, rows[r0:r0 + int(rows_per_call)], H, W)
             uv, a = mapping(xyt), F_Alpha(xyt).reshape(-1)
             keep = (-a if invert_alpha else a) > alpha_thresh
             if bool(keep.any()):
@@ -482,12 +478,9 @@ def edit_atlas(models, res_x, res_y, number_of_frames, tex_fg, box_fg, tex_bg, b
     a chunk costs four launches (FG_UV_Mapping, BG_UV_Mapping, F_Alpha, ops.atlas_edit), five when a texture is RGBA
     (ONE F_Atlas launch gives both base colours).  mask_fg holds the true maximum of alpha per texel; the reference keeps
     the last writer among the rows of one batch that share a texel."""
-    FG, BG, F_Atlas, F_Alpha = (models[k] for k in ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Atlas', 'F_Alpha'))
-    device = next(FG.parameters()).device
-    W, H, T = int(res_x), int(res_y), int(number_of_frames)
-    frames = list(range(T)) if frames is None else [int(f) for f in frames]
-    if any(not 0 <= f < T for f in frames):
-        raise ValueError(f'frames {frames} outside 0 .. {T - 1}')
+    device = next(models['FG_UV_Mapping'].parameters()).device
+    W, H = int(res_x), int(res_y)
+    n, chunks = _pixel_chunks(W, H, number_of_frames, frames, rows_per_call, device)
     tex_fg = torch.as_tensor(tex_fg).to(device=device, dtype=torch.float32).contiguous()
     tex_bg = torch.as_tensor(tex_bg).to(device=device, dtype=torch.float32).contiguous()
     for name, tex in (('tex_fg', tex_fg), ('tex_bg', tex_bg)):
@@ -498,31 +491,20 @@ def edit_atlas(models, res_x, res_y, number_of_frames, tex_fg, box_fg, tex_bg, b
     masks = None
     if want_masks:
         masks = tuple(torch.zeros(t.shape[0], t.shape[1], dtype=torch.float32, device=device) for t in (tex_fg, tex_bg))
-    xs, ys, ts = _pixel_axes(W, H, T, device)
-    ts = ts[torch.tensor(frames, dtype=torch.long, device=device)] if frames else ts[:0]
-    total = len(frames) * H * W
-    edit, fg, bg = (torch.empty(total, 3, dtype=torch.float32, device=device) for _ in range(3))
-    relevant = torch.empty(total, dtype=torch.uint8, device=device)
-    alpha = torch.empty(total, dtype=torch.float32, device=device)
+    edit, fg, bg = (torch.empty(n * H * W, 3, dtype=torch.float32, device=device) for _ in range(3))
+    relevant = torch.empty(n * H * W, dtype=torch.uint8, device=device)
+    alpha = torch.empty(n * H * W, dtype=torch.float32, device=device)
     launches = 0
     with torch.no_grad():
-        for r0 in range(0, total, int(rows_per_call)):
-            r1 = min(r0 + int(rows_per_call), total)
-            xyt = _chunk_xyt(xs, ys, ts, r0, r1, H, W)
-            uv1, uv2, a = FG(xyt), BG(xyt), F_Alpha(xyt)
-            a = 0.5 * (a + 1.0)
-            a = a * 0.99
-            a = (a + 0.001).reshape(-1)
-            base1 = base2 = None
-            if overlay:
-                both = F_Atlas(torch.cat((uv1 * 0.5 + 0.5, uv2 * 0.5 - 0.5), dim=0))
-                base1, base2 = ((both[:r1 - r0] + 1) * 0.5).contiguous(), ((both[r1 - r0:] + 1) * 0.5).contiguous()
+        for r0, r1, xyt in chunks:
+            uv1, uv2, a = _mappings_and_alpha(models, xyt)
+            a = a.reshape(-1)
+            base1, base2 = _atlas_colours(models['F_Atlas'], uv1, uv2) if overlay else (None, None)
             edit[r0:r1], fg[r0:r1], bg[r0:r1], relevant[r0:r1] = ops.atlas_edit(
                 uv1, uv2, a, tex_fg, box_fg, tex_bg, box_bg, base_fg=base1 if tex_fg.shape[-1] == 4 else None,
                 base_bg=base2 if tex_bg.shape[-1] == 4 else None, masks=masks)
             alpha[r0:r1] = a
             launches += 5 if overlay else 4
-    n = len(frames)
     return dict(edit=edit.view(n, H, W, 3), edited_fg=fg.view(n, H, W, 3), edited_bg=bg.view(n, H, W, 3),
                 relevant=relevant.view(n, H, W), alpha=alpha.view(n, H, W), mask_fg=masks[0] if masks else None,
                 mask_bg=masks[1] if masks else None, launches=launches)

@@ -305,8 +305,32 @@ long cm_packed_floats(int64_t enc, int64_t hidden_dim, int64_t mlp_layers, int64
     return total;
 }
 
-// the layer stack's part of the kernel arguments (p.enc / p.encp set by the caller)
-void cm_fill_layers(CoordMlpParams& p, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask) {
+// The layer stack's half of an entry point: validates it (every message under `what`; the unsupported options before
+// N == 0, which the CALLER answers with VSX_OK after this returns VSX_OK) and fills the kernel arguments for `enc` encoded
+// columns; pe_dim 0: the columns are not the sin/cos encoding.
+int cm_prepare(const char* what, CoordMlpParams& p, const float* x, int64_t N, int64_t input_dim, int64_t output_dim,
+               int64_t hidden_dim, int64_t mlp_layers, int64_t pe_dim, int64_t enc, int64_t skip_mask, int64_t use_tanh,
+               const float* packed, int64_t packed_floats, float* out) {
+    VSX_REQUIRE(output_dim >= 1 && output_dim <= 3, VSX_E_UNSUPPORTED, "%s: output_dim %lld (1 to 3)", what, (long long)output_dim);
+    VSX_REQUIRE(hidden_dim >= 32 && hidden_dim <= 256 && hidden_dim % 32 == 0, VSX_E_UNSUPPORTED,
+                "%s: hidden_dim %lld (a multiple of 32 up to 256)", what, (long long)hidden_dim);
+    VSX_REQUIRE(mlp_layers >= 2 && mlp_layers <= CM_MAX_LAYERS, VSX_E_UNSUPPORTED, "%s: mlp_layers %lld (2 to 8)", what,
+                (long long)mlp_layers);
+    VSX_REQUIRE(skip_mask >= 0 && (skip_mask & 1) == 0 && (skip_mask >> mlp_layers) == 0, VSX_E_UNSUPPORTED,
+                "%s: skip_layers must lie in 1 .. mlp_layers - 1 (mask 0x%llx)", what, (long long)skip_mask);
+    VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "%s: N = %lld", what, (long long)N);
+    if (N == 0) return VSX_OK;
+    VSX_REQUIRE(x && packed && out, VSX_E_BADSHAPE, "%s: null argument", what);
+    VSX_REQUIRE(vsx_aligned16(packed), VSX_E_BADSHAPE, "%s: packed weights must be 16-byte aligned", what);
+    const int64_t need = cm_packed_floats(enc, hidden_dim, mlp_layers, skip_mask);
+    VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "%s: packed weights hold %lld floats, this network needs %lld", what,
+                (long long)packed_floats, (long long)need);
+
+    p.x = x, p.w = packed, p.out = out, p.N = N;
+    p.in_dim = (int)input_dim, p.out_dim = (int)output_dim, p.hidden = (int)hidden_dim, p.layers = (int)mlp_layers;
+    p.pe_dim = (int)pe_dim;
+    p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
+    p.skip_mask = (int)skip_mask, p.use_tanh = use_tanh != 0;
     long off = 0;
     for (int l = 0; l < CM_MAX_LAYERS; ++l) {
         p.w_off[l] = p.b_off[l] = 0;
@@ -316,6 +340,7 @@ void cm_fill_layers(CoordMlpParams& p, int64_t hidden_dim, int64_t mlp_layers, i
         p.w_off[l] = (int)off, p.b_off[l] = (int)(off + fp * kp);
         off += fp * kp + fp;
     }
+    return VSX_OK;
 }
 
 template <class Grid>
@@ -394,31 +419,13 @@ extern "C" int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, i
     VSX_REQUIRE(pe_type == 0 || pe_type == 1, VSX_E_UNSUPPORTED,
                 "coord_mlp: pe_type 'hash_encoding' (%lld) is not implemented, only 'none' and 'encoding'", (long long)pe_type);
     VSX_REQUIRE(input_dim == 2 || input_dim == 3, VSX_E_UNSUPPORTED, "coord_mlp: input_dim %lld (2 or 3)", (long long)input_dim);
-    VSX_REQUIRE(output_dim >= 1 && output_dim <= 3, VSX_E_UNSUPPORTED, "coord_mlp: output_dim %lld (1 to 3)", (long long)output_dim);
-    VSX_REQUIRE(hidden_dim >= 32 && hidden_dim <= 256 && hidden_dim % 32 == 0, VSX_E_UNSUPPORTED,
-                "coord_mlp: hidden_dim %lld (a multiple of 32 up to 256)", (long long)hidden_dim);
-    VSX_REQUIRE(mlp_layers >= 2 && mlp_layers <= CM_MAX_LAYERS, VSX_E_UNSUPPORTED, "coord_mlp: mlp_layers %lld (2 to 8)",
-                (long long)mlp_layers);
-    const long enc = pe_type == 1 ? 2 * input_dim * pe_dim : input_dim;
+    const int64_t enc = pe_type == 1 ? 2 * input_dim * pe_dim : input_dim;
     VSX_REQUIRE(pe_type == 0 || (pe_dim >= 1 && enc <= CM_MAX_ENC), VSX_E_UNSUPPORTED,
                 "coord_mlp: pe_dim %lld (2 * input_dim * pe_dim must be 1 to %d)", (long long)pe_dim, CM_MAX_ENC);
-    VSX_REQUIRE(skip_mask >= 0 && (skip_mask & 1) == 0 && (skip_mask >> mlp_layers) == 0, VSX_E_UNSUPPORTED,
-                "coord_mlp: skip_layers must lie in 1 .. mlp_layers - 1 (mask 0x%llx)", (long long)skip_mask);
-    VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "coord_mlp: N = %lld", (long long)N);
-    if (N == 0) return VSX_OK;
-    VSX_REQUIRE(x && packed && out, VSX_E_BADSHAPE, "coord_mlp: null argument");
-    VSX_REQUIRE(vsx_aligned16(packed), VSX_E_BADSHAPE, "coord_mlp: packed weights must be 16-byte aligned");
-    const int64_t need = cm_packed_floats(enc, hidden_dim, mlp_layers, skip_mask);
-    VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "coord_mlp: packed weights hold %lld floats, this network needs %lld",
-                (long long)packed_floats, (long long)need);
-
     CoordMlpParams p;
-    p.x = x, p.w = packed, p.out = out, p.N = N;
-    p.in_dim = (int)input_dim, p.out_dim = (int)output_dim, p.hidden = (int)hidden_dim, p.layers = (int)mlp_layers;
-    p.pe_dim = pe_type == 1 ? (int)pe_dim : 0;
-    p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
-    p.skip_mask = (int)skip_mask, p.use_tanh = use_tanh != 0;
-    cm_fill_layers(p, hidden_dim, mlp_layers, skip_mask);
+    const int rc = cm_prepare("coord_mlp", p, x, N, input_dim, output_dim, hidden_dim, mlp_layers, pe_type == 1 ? pe_dim : 0, enc,
+                              skip_mask, use_tanh, packed, packed_floats, out);
+    if (rc != VSX_OK || N == 0) return rc;
     return cm_launch("vsx_coord_mlp_f32", p, NoGrid{}, stream);
 }
 
@@ -463,29 +470,12 @@ extern "C" int vsx_hash_mlp_f32(const float* x, int64_t N, int64_t input_dim, co
     const int rc = hg_fill("hash_mlp", g, input_dim, table, table_floats, n_levels, n_features, log2_hashmap_size,
                            base_resolution, per_level_scale);
     if (rc != VSX_OK) return rc;
-    VSX_REQUIRE(output_dim >= 1 && output_dim <= 3, VSX_E_UNSUPPORTED, "hash_mlp: output_dim %lld (1 to 3)", (long long)output_dim);
-    VSX_REQUIRE(hidden_dim >= 32 && hidden_dim <= 256 && hidden_dim % 32 == 0, VSX_E_UNSUPPORTED,
-                "hash_mlp: hidden_dim %lld (a multiple of 32 up to 256)", (long long)hidden_dim);
-    VSX_REQUIRE(mlp_layers >= 2 && mlp_layers <= CM_MAX_LAYERS, VSX_E_UNSUPPORTED, "hash_mlp: mlp_layers %lld (2 to 8)",
-                (long long)mlp_layers);
-    VSX_REQUIRE(skip_mask >= 0 && (skip_mask & 1) == 0 && (skip_mask >> mlp_layers) == 0, VSX_E_UNSUPPORTED,
-                "hash_mlp: skip_layers must lie in 1 .. mlp_layers - 1 (mask 0x%llx)", (long long)skip_mask);
-    VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "hash_mlp: N = %lld", (long long)N);
-    if (N == 0) return VSX_OK;
-    VSX_REQUIRE(x && table && packed && out, VSX_E_BADSHAPE, "hash_mlp: null argument");
-    VSX_REQUIRE(vsx_aligned16(table), VSX_E_BADSHAPE, "hash_mlp: the grid table must be 16-byte aligned");
-    VSX_REQUIRE(vsx_aligned16(packed), VSX_E_BADSHAPE, "hash_mlp: packed weights must be 16-byte aligned");
-    const long enc = n_levels * n_features;
-    const int64_t need = cm_packed_floats(enc, hidden_dim, mlp_layers, skip_mask);
-    VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "hash_mlp: packed weights hold %lld floats, this network needs %lld",
-                (long long)packed_floats, (long long)need);
-
+    // the table's own checks, ahead of the packed buffer's as they always were; N <= 0 is cm_prepare's to answer
+    VSX_REQUIRE(N <= 0 || table, VSX_E_BADSHAPE, "hash_mlp: null argument");
+    VSX_REQUIRE(N <= 0 || vsx_aligned16(table), VSX_E_BADSHAPE, "hash_mlp: the grid table must be 16-byte aligned");
     CoordMlpParams p;
-    p.x = x, p.w = packed, p.out = out, p.N = N;
-    p.in_dim = 2, p.out_dim = (int)output_dim, p.hidden = (int)hidden_dim, p.layers = (int)mlp_layers;
-    p.pe_dim = 0;
-    p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
-    p.skip_mask = (int)skip_mask, p.use_tanh = use_tanh != 0;
-    cm_fill_layers(p, hidden_dim, mlp_layers, skip_mask);
+    const int prc = cm_prepare("hash_mlp", p, x, N, 2, output_dim, hidden_dim, mlp_layers, 0, n_levels * n_features, skip_mask,
+                               use_tanh, packed, packed_floats, out);
+    if (prc != VSX_OK || N == 0) return prc;
     return cm_launch("vsx_hash_mlp_f32", p, g, stream);
 }

@@ -24,32 +24,25 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .render_atlas import IMAGE_EXT, _save_image
+from .atlas_cli import add_atlas_arguments, add_frame_arguments, open_atlas, parse_frames
+from .render_atlas import IMAGE_EXT, _save_image, write_frames
 
 
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m videoswap_amd.edit_atlas', description=__doc__.split('\n')[0])
-    p.add_argument('--atlas_config_path', required=True, help="the atlas's training YAML (models.*, datasets.*)")
-    p.add_argument('--atlas_model_path', required=True, help='checkpoint with the five networks')
+    add_atlas_arguments(p, 'the five networks')
     p.add_argument('--save_dir', required=True)
     p.add_argument('--render_dir', required=True, help='output directory of videoswap_amd.render_atlas (summary.json, texture_orig*.png)')
     p.add_argument('--edit_fg', default=None, help='edited foreground texture (RGB replaces, RGBA overlays); default: texture_orig1.png')
     p.add_argument('--edit_bg', default=None, help='edited background texture (RGB replaces, RGBA overlays); default: texture_orig2.png')
-    p.add_argument('--num_frames', type=int, default=None, help='stands in for the file count of datasets.frame_path')
-    p.add_argument('--frames', default=None, help='comma-separated frame indices to render (default: all)')
+    add_frame_arguments(p)
     p.add_argument('--checkerboard', action='store_true', help='also write the checkerboard composites')
     p.add_argument('--write_masks', action='store_true', help='also write texture_edit1.png / texture_edit2.png')
     return p
 
 
 def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
-    if args.frames is not None:
-        try:
-            args.frames = [int(v) for v in args.frames.split(',') if v.strip() != '']
-        except ValueError:
-            raise SystemExit(f'--frames: {args.frames!r} is not a comma-separated list of frame indices') from None
-    return args
+    return parse_frames(build_parser().parse_args(argv))
 
 
 def _read_texture(path):
@@ -65,15 +58,10 @@ def _read_texture(path):
 
 def run(args, device=None):
     from . import atlas
-    if device is None:
-        device = torch.device('cuda')         # the networks and the edit run on the HIP kernels only
     with open(os.path.join(args.render_dir, 'summary.json')) as fr:
         rendered = json.load(fr)
-    config = atlas.load_atlas_config(args.atlas_config_path)
-    models = atlas.load_atlas_render_models(config, args.atlas_model_path, device=device)
-    T = atlas.number_of_frames(config, args.num_frames if args.num_frames is not None else rendered.get('number_of_frames'))
-    W, H = int(config['datasets']['res_x']), int(config['datasets']['res_y'])
-    frames = list(range(T)) if args.frames is None else args.frames
+    num_frames = args.num_frames if args.num_frames is not None else rendered.get('number_of_frames')
+    models, T, W, H, frames, device = open_atlas(args, device, atlas.RENDER_MODEL_NAMES, num_frames)
 
     tex_fg = _read_texture(args.edit_fg or os.path.join(args.render_dir, 'texture_orig1.png')).to(device)
     tex_bg = _read_texture(args.edit_bg or os.path.join(args.render_dir, 'texture_orig2.png')).to(device)
@@ -84,9 +72,7 @@ def run(args, device=None):
     out = atlas.edit_atlas(models, W, H, T, tex_fg, box_fg, tex_bg, box_bg, frames=frames, want_masks=args.write_masks)
     launches = out['launches']
     for sub in ('edit', 'edited_fg', 'edited_bg'):
-        os.makedirs(os.path.join(args.save_dir, sub), exist_ok=True)
-        for k, f in enumerate(frames):
-            _save_image(out[sub][k], os.path.join(args.save_dir, sub, f'{f:05d}.png'))
+        write_frames(args.save_dir, sub, out[sub], frames)
     if args.write_masks:                                                                       # evaluate_model:436-444
         _save_image(out['mask_fg'].unsqueeze(-1) * tex_fg[..., :3], os.path.join(args.save_dir, 'texture_edit1.png'))
         _save_image(out['mask_bg'].unsqueeze(-1) * tex_bg[..., :3], os.path.join(args.save_dir, 'texture_edit2.png'))
@@ -96,9 +82,7 @@ def run(args, device=None):
                                            (area_bg['minx'], area_bg['miny'], area_bg['edge_size']), frames=frames)
         launches += boards['launches']
         for sub in ('checkerboard_fg', 'checkerboard_bg'):
-            os.makedirs(os.path.join(args.save_dir, sub), exist_ok=True)
-            for k, f in enumerate(frames):
-                _save_image(boards[sub][k], os.path.join(args.save_dir, sub, f'{f:05d}.png'))
+            write_frames(args.save_dir, sub, boards[sub], frames)
 
     rel = out['relevant']
     n = max(rel.numel(), 1)

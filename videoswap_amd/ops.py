@@ -802,6 +802,23 @@ _COORD_PE = {'none': 0, 'encoding': 1, 'hash_encoding': 2}
 _COORD_MLP = {'origin': 0, 'tcnn': 1}
 
 
+def _skip_mask(skip_layers, what):
+    """skip_layers -> the bit mask the entry points take (bit i: layer i sees the encoded input again)"""
+    mask = 0
+    for i in skip_layers:
+        if not 0 <= int(i) < 62:
+            raise NotImplementedError(f'{what}: skip_layers {list(skip_layers)}')
+        mask |= 1 << int(i)
+    return mask
+
+
+def _check_supported(rc, what):
+    """`check`, with VSX_E_UNSUPPORTED (an option the kernel does not implement) as NotImplementedError"""
+    if rc == _lib.VSX_E_UNSUPPORTED:
+        raise NotImplementedError(_lib.load().vsx_last_error().decode(errors='replace'))
+    check(rc, what)
+
+
 def coord_mlp(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type='none', pe_dim=0, mlp_type='origin',
               skip_layers=(), use_tanh=True):
     """The whole network of IMLP_Hash.forward (mlp_type 'origin') in one launch, fp32 throughout: x fp32 [N, input_dim]
@@ -815,19 +832,13 @@ def coord_mlp(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type=
     _chk(packed, 'packed', torch.float32)
     if x.dim() != 2 or x.shape[1] != input_dim:
         raise _lib.VsxError(f'coord_mlp: x must be [N, {input_dim}], got {tuple(x.shape)}')
-    mask = 0
-    for i in skip_layers:
-        if not 0 <= int(i) < 62:
-            raise NotImplementedError(f'coord_mlp: skip_layers {list(skip_layers)}')
-        mask |= 1 << int(i)
+    mask = _skip_mask(skip_layers, 'coord_mlp')
     out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
     lib = _lib.load()
     rc = lib.vsx_coord_mlp_f32(_p(x), x.shape[0], int(input_dim), int(output_dim), int(hidden_dim), int(mlp_layers),
                                _COORD_PE[pe_type], int(pe_dim), _COORD_MLP[mlp_type], mask, int(bool(use_tanh)),
                                _p(packed), packed.numel(), _p(out), _stream())
-    if rc == _lib.VSX_E_UNSUPPORTED:
-        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
-    check(rc, 'vsx_coord_mlp_f32')
+    _check_supported(rc, 'vsx_coord_mlp_f32')
     return out
 
 
@@ -849,9 +860,7 @@ def hash_grid(x, table, grid):
     out = torch.empty(x.shape[0], cfg[0] * cfg[1], dtype=torch.float32, device=x.device)
     lib = _lib.load()
     rc = lib.vsx_hash_grid_f32(_p(x), x.shape[0], d, tab, floats, *cfg, _p(out), _stream())
-    if rc == _lib.VSX_E_UNSUPPORTED:
-        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
-    check(rc, 'vsx_hash_grid_f32')
+    _check_supported(rc, 'vsx_hash_grid_f32')
     return out
 
 
@@ -861,18 +870,12 @@ def hash_mlp(x, table, grid, packed, output_dim, hidden_dim, mlp_layers, skip_la
     -> fp32 [N, output_dim]."""
     d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_mlp')
     _chk(packed, 'packed', torch.float32)
-    mask = 0
-    for i in skip_layers:
-        if not 0 <= int(i) < 62:
-            raise NotImplementedError(f'hash_mlp: skip_layers {list(skip_layers)}')
-        mask |= 1 << int(i)
+    mask = _skip_mask(skip_layers, 'hash_mlp')
     out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
     lib = _lib.load()
     rc = lib.vsx_hash_mlp_f32(_p(x), x.shape[0], d, tab, floats, *cfg, int(output_dim), int(hidden_dim), int(mlp_layers),
                               mask, int(bool(use_tanh)), _p(packed), packed.numel(), _p(out), _stream())
-    if rc == _lib.VSX_E_UNSUPPORTED:
-        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
-    check(rc, 'vsx_hash_mlp_f32')
+    _check_supported(rc, 'vsx_hash_mlp_f32')
     return out
 
 
@@ -907,9 +910,7 @@ def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None
     relevant = torch.empty(N, dtype=torch.uint8, device=uv_fg.device)
     lib = _lib.load()
     rc = lib.vsx_atlas_edit_f32(_p(uv_fg), _p(uv_bg), _p(alpha), N, *layers, _p(edit), _p(fg), _p(bg), _p(relevant), _stream())
-    if rc == _lib.VSX_E_UNSUPPORTED:
-        raise NotImplementedError(lib.vsx_last_error().decode(errors='replace'))
-    check(rc, 'vsx_atlas_edit_f32')
+    _check_supported(rc, 'vsx_atlas_edit_f32')
     return edit, fg, bg, relevant
 
 

@@ -9,17 +9,16 @@ produced.
 import argparse
 import os
 
-import torch
+from .atlas_cli import add_atlas_arguments, add_frame_arguments, open_atlas
 
 
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m videoswap_amd.propagate_points', description=__doc__.split('\n')[0])
-    p.add_argument('--atlas_config_path', required=True, help="the atlas's training YAML (models.*, datasets.*)")
-    p.add_argument('--atlas_model_path', required=True, help='checkpoint with FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha')
+    add_atlas_arguments(p, 'FG_UV_Mapping, FG_UV_Mapping_Inverse, F_Alpha')
     p.add_argument('--source_point_path', required=True, help='<keyframe index>.json: {name: [y, x]}')
     p.add_argument('--source_tap_path', required=True)
     p.add_argument('--target_point_path', required=True, help='{name: [y, x]} of the dragged points')
-    p.add_argument('--num_frames', type=int, default=None, help='stands in for the file count of datasets.frame_path')
+    add_frame_arguments(p, frames=False)
     p.add_argument('--save_path', default=None, help='default: TAP_<target stem>.pth beside the target file')
     return p
 
@@ -39,14 +38,10 @@ def parse_args(argv=None):
 
 def run(args, device=None):
     from . import atlas, formats
-    if device is None:
-        device = torch.device('cuda')         # the networks run on the HIP kernel only
-    config = atlas.load_atlas_config(args.atlas_config_path)
-    models = atlas.load_atlas_models(config, args.atlas_model_path, device=device)
-    T = atlas.number_of_frames(config, args.num_frames)
-    larger_dim = max(int(config['datasets']['res_x']), int(config['datasets']['res_y']))
-    tap = atlas.propagate_point_sequence(args.source_point_path, args.source_tap_path, args.target_point_path, *models,
-                                         larger_dim=larger_dim, number_of_frames=T, device=device)
+    models, T, W, H, _, device = open_atlas(args, device, atlas.MODEL_NAMES, args.num_frames)
+    tap = atlas.propagate_point_sequence(args.source_point_path, args.source_tap_path, args.target_point_path,
+                                         *(models[k] for k in atlas.MODEL_NAMES), larger_dim=max(W, H), number_of_frames=T,
+                                         device=device)
     formats.save_tap(args.save_path, tap['pred_tracks'], tap['point_embedding'], tap['point_name2id'])
     print(f'save to {args.save_path}')
     return tap

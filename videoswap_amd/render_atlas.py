@@ -19,30 +19,24 @@ import numpy as np
 import torch
 from PIL import Image
 
+from .atlas_cli import add_atlas_arguments, add_frame_arguments, open_atlas, parse_frames
+
 IMAGE_EXT = ('.png', '.jpg', '.jpeg', '.bmp')
 
 
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m videoswap_amd.render_atlas', description=__doc__.split('\n')[0])
-    p.add_argument('--atlas_config_path', required=True, help="the atlas's training YAML (models.*, datasets.*)")
-    p.add_argument('--atlas_model_path', required=True, help='checkpoint with the five networks')
+    add_atlas_arguments(p, 'the five networks')
     p.add_argument('--save_dir', required=True)
     p.add_argument('--frame_dir', default=None, help='video frames to compute the PSNR against')
     p.add_argument('--mask_dir', default=None, help='foreground masks (for the foreground box)')
-    p.add_argument('--num_frames', type=int, default=None, help='stands in for the file count of datasets.frame_path')
-    p.add_argument('--frames', default=None, help='comma-separated frame indices to render (default: all)')
+    add_frame_arguments(p)
     p.add_argument('--texture_resolution', type=int, default=1000)
     return p
 
 
 def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
-    if args.frames is not None:
-        try:
-            args.frames = [int(v) for v in args.frames.split(',') if v.strip() != '']
-        except ValueError:
-            raise SystemExit(f'--frames: {args.frames!r} is not a comma-separated list of frame indices') from None
-    return args
+    return parse_frames(build_parser().parse_args(argv))
 
 
 def _read_images(directory, indices, size, mode):
@@ -64,25 +58,23 @@ def _save_image(array01, path):
     Image.fromarray((array01.clamp(0, 1) * 255).round().to(torch.uint8).cpu().numpy()).save(path)
 
 
+def write_frames(save_dir, sub, images, frames):
+    """images[k] -> <save_dir>/<sub>/<frames[k]>.png"""
+    os.makedirs(os.path.join(save_dir, sub), exist_ok=True)
+    for k, f in enumerate(frames):
+        _save_image(images[k], os.path.join(save_dir, sub, f'{f:05d}.png'))
+
+
 def run(args, device=None):
     from . import atlas
-    if device is None:
-        device = torch.device('cuda')         # the networks run on the HIP kernels only
-    config = atlas.load_atlas_config(args.atlas_config_path)
-    models = atlas.load_atlas_render_models(config, args.atlas_model_path, device=device)
     num_frames = args.num_frames
     if num_frames is None and args.frame_dir:
         num_frames = len([n for n in os.listdir(args.frame_dir) if n.lower().endswith(IMAGE_EXT)])
-    T = atlas.number_of_frames(config, num_frames)
-    W, H = int(config['datasets']['res_x']), int(config['datasets']['res_y'])
-    frames = list(range(T)) if args.frames is None else args.frames
+    models, T, W, H, frames, _ = open_atlas(args, device, atlas.RENDER_MODEL_NAMES, num_frames)
 
     out = atlas.render_atlas(models, W, H, T, frames=frames)
     for sub in ('reconstruction', 'alpha'):
-        os.makedirs(os.path.join(args.save_dir, sub), exist_ok=True)
-    for k, f in enumerate(frames):
-        _save_image(out['reconstruction'][k], os.path.join(args.save_dir, 'reconstruction', f'{f:05d}.png'))
-        _save_image(out['alpha'][k], os.path.join(args.save_dir, 'alpha', f'{f:05d}.png'))
+        write_frames(args.save_dir, sub, out[sub], frames)
     launches = out['launches']
 
     # the two boxes of evaluate_model:217-220 (over ALL frames of the atlas, as there)
