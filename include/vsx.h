@@ -49,7 +49,8 @@ const char* vsx_source_digest(void);
  * 2 always-when-eligible use of the persistent ping-pong GEMM kernel; "pp_sched" = its option bits (8: linear tile walk; 4: convolutions sum K
  * tap-major like the tile kernels instead of taps-inner; 16: a private A slab per convolution tap; 32: common piece order in every CU).  Results
  * are identical for every setting except bit 4 (same arithmetic; bit 4 selects another fp32 summation order of the same products).
- * "tile_tune" (diagnostics, tools/small_m_sweep.py) forces a tile / ring depth / K-slice count of the workgroup-per-tile kernels. */
+ * "tile_tune" (diagnostics, tools/small_m_sweep.py) forces a tile / ring depth / K-slice count of the workgroup-per-tile kernels.
+ * "conv_winograd" = 0 never / 1 default / 2 always-when-supported: what vsx_conv3x3_winograd_auto answers (below). */
 int vsx_set_option(const char* name, int64_t value);
 
 /* ------------------------------------------------------------------------------------------
@@ -140,6 +141,27 @@ int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d);
 /* bytes of `workspace` with which vsx_gemm_f16(d) takes the split-K path under the current options; 0: it would not split whatever it
    is given (another kernel takes the problem, or d does not pass the checks of vsx_gemm_f16) */
 int64_t vsx_gemm_workspace(const vsx_gemm_desc* d);
+
+/* Winograd F(2x2, 3x3) form of the stride-1 3x3 convolution (InflatedConv3d 3x3 of the resnets, resnet.py:9-18,170,181):
+ * the SAME description as vsx_gemm_f16 would take, computed as an input transform V = B^T d B ([16][M/4][C1+C2]), sixteen
+ * GEMMs [M/4, C1+C2] x [N, C1+C2]^T in one batched vsx_gemm_f16 launch, and an output transform A^T Mt A followed by the
+ * direct path's epilogue in its order (+ bias, + rowvec row, + residual last): 16 multiplications per 2 x 2 output tile
+ * and channel pair instead of 36 (csrc/winograd.hip).  fp32 transform arithmetic; V, U, Mt and the output are rounded to
+ * fp16 once each, so the result differs from vsx_gemm_f16's by rounding (about twice its error against fp64).
+ *   U: the transformed weights G g G^T, fp16 [16][N][C1+C2] (xi = 4 a + b outermost), made by the caller from B =
+ *      [N, 3, 3, C1+C2] (videoswap_amd.ops.winograd_weights); d->B is not read.
+ *   workspace: caller-allocated, 16-byte aligned, vsx_conv3x3_winograd_workspace(d) bytes (V, then Mt); that function
+ *      returns 0 for a description this form does not take.
+ *   Supported: a_mode 1, ks 3, stride 1, upsample 0, symmetric padding 1 (pad_lo = pad_hi = -1 or 1), H and W even, no
+ *      batch, C1 / C2 / N multiples of 8 (two sources: C1, C2 multiples of 64), ldc / ldr multiples of 8, alpha 1,
+ *      epilogue = bias / rowvec / residual.  Anything else: VSX_E_UNSUPPORTED; the library never falls back by itself.
+ * vsx_conv3x3_winograd_auto(d): 1 where the caller should take this form under the current options ("conv_winograd":
+ *   0 never, 1 = supported, (C1 + C2 >= 640 and H * W <= 256) or (C1 + C2 >= 1280 and H * W <= 1024), and no GEMM back end
+ *   forced through "gemm_pp" / "tile_tune", 2 = whenever supported), else 0. */
+int64_t vsx_conv3x3_winograd_workspace(const vsx_gemm_desc* d);
+int64_t vsx_conv3x3_winograd_auto(const vsx_gemm_desc* d);
+int vsx_conv3x3_winograd_f16(const vsx_gemm_desc* d, const void* U, void* workspace, int64_t workspace_bytes,
+                             vsx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * K3: GroupNorm over channels-last activations, two kernels.

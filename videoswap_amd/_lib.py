@@ -60,6 +60,10 @@ PROTOTYPES = {
     'vsx_gemm_f16': (c_int, [POINTER(GemmDesc), c_void_p]),
     'vsx_gemm_workspace': (c_int64, [POINTER(GemmDesc)]),
     'vsx_gemm_rowstats_parts': (c_int64, [POINTER(GemmDesc)]),
+    # Winograd F(2x2, 3x3) form of the stride-1 3x3 convolutions (csrc/winograd.hip)
+    'vsx_conv3x3_winograd_workspace': (c_int64, [POINTER(GemmDesc)]),
+    'vsx_conv3x3_winograd_auto': (c_int64, [POINTER(GemmDesc)]),
+    'vsx_conv3x3_winograd_f16': (c_int, [POINTER(GemmDesc), c_void_p, c_void_p, c_int64, c_void_p]),
     'vsx_groupnorm_chunks': (c_int64, [c_int64, c_int64]),
     'vsx_groupnorm_stats': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                     c_void_p]),

@@ -148,8 +148,9 @@ class _Conv2d(torch.autograd.Function):
     def forward(ctx, x, x2, residual, weight, bias, rowvec, stride, upsample, rows_per_vec, padding):
         if padding is not None:
             raise NotImplementedError('conv2d with explicit padding on the gradient path (VAE only: frozen)')
-        out = _k('conv2d')(x, weight, bias, x2=x2, stride=stride, upsample=upsample, rowvec=rowvec,
-                           rows_per_vec=rows_per_vec, residual=residual)
+        with ops.winograd_suspended():      # the training step stays on the direct kernels, forward and dgrad
+            out = _k('conv2d')(x, weight, bias, x2=x2, stride=stride, upsample=upsample, rowvec=rowvec,
+                               rows_per_vec=rows_per_vec, residual=residual)
         ctx.stride, ctx.upsample = stride, upsample
         ctx.xshape = x.shape
         ctx.c1 = x.shape[-1]
@@ -177,7 +178,8 @@ class _Conv2d(torch.autograd.Function):
             c1, c2 = ctx.c1, ctx.c2
 
             def dgrad(lo, hi):
-                d = _k('conv2d')(src, wd[lo:hi])
+                with ops.winograd_suspended():
+                    d = _k('conv2d')(src, wd[lo:hi])
                 return _k('sum_pool2x2')(d) if ctx.upsample else d
             if _need(ctx, 0):
                 dx = dgrad(0, c1)

@@ -29,6 +29,9 @@
 //                                            K = N = 320 launches from 131 072 rows
 //   ws_waves      VSX_WS_WAVES      10       weight-stationary kernel: 10 waves of 32 columns or 5 waves of 64 (= row-statistics parts per
 //                                            320 columns)
+//   conv_winograd VSX_CONV_WINOGRAD 1        Winograd F(2x2, 3x3) form of the stride-1 3x3 convolutions (winograd.hip): 0 = never, 1 = the
+//                                            shapes of vsx_conv3x3_winograd_auto unless a GEMM back end is forced (gemm_pp != 1 or
+//                                            tile_tune != 0), 2 = every supported description (tests)
 #include "options.h"
 
 #include <stdlib.h>
@@ -43,7 +46,8 @@ Option g_options[] = {{"gemm_pp", "VSX_GEMM_PP", 1, false}, {"pp_sched", "VSX_PP
                       {"tile_tune", "VSX_TUNE_TILE", 0, false}, {"xcd_walk", "VSX_XCD_WALK", 1, false},
                       {"attn_qb", "VSX_ATTN_QB", 0, false}, {"temporal_out", "VSX_TEMPORAL_OUT", 0, false},
                       {"attn_o16", "VSX_ATTN_O16", 0, false}, {"gn_fuse", "VSX_GN_FUSE", 0, false},
-                      {"gemm_ws", "VSX_GEMM_WS", 1, false}, {"ws_waves", "VSX_WS_WAVES", 10, false}};
+                      {"gemm_ws", "VSX_GEMM_WS", 1, false}, {"ws_waves", "VSX_WS_WAVES", 10, false},
+                      {"conv_winograd", "VSX_CONV_WINOGRAD", 1, false}};
 Option* find_option(const char* name) {
     for (auto& o : g_options)
         if (strcmp(o.name, name) == 0) {

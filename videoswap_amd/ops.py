@@ -4,6 +4,7 @@ PyTorch is used for device memory and the HIP stream only: every function here t
 (ROCm) tensors, hands raw pointers + the current stream to a hand-written gfx950 kernel and
 returns the output tensor.  There is no fallback implementation.
 """
+import contextlib
 import ctypes
 import os
 
@@ -191,6 +192,7 @@ def fold_cache_tensors():
         out.extend((hit[2], hit[3], hit[4]))
         out.extend(hit[5].values())
     out.extend(hit[2] for hit in _subpixel_cache.values())
+    out.extend(hit[2] for hit in _winograd_cache.values())
     return out
 
 
@@ -391,6 +393,91 @@ def _subpixel_eligible(nimg, Hs, Ws, C1, Cout, ks, stride, x2, rowvec, residual,
     return mc % 256 == 0 and (4 * mc // 256) * (Cout // 320) >= 192
 
 
+# VSX_CONV_WINOGRAD (library option "conv_winograd"): 0 = the stride-1 3x3 convolutions always on the direct kernels,
+# 1 = Winograd F(2x2, 3x3) where it measured faster (`_winograd_eligible`), 2 = wherever the form is supported (tests)
+_winograd_cache = {}      # id(weight) -> (stamp, weight ref, [16, Cout, C] fp16)
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+_winograd_hold = [0]      # > 0: the gradient path is calling (videoswap_amd/autograd.py) — the training step keeps the direct kernels
+
+
+@contextlib.contextmanager
+def winograd_suspended():
+    """The convolutions launched inside take the direct kernels whatever the option says: the adapter training step's forward
+    and dgrad convolutions (flipped weight copies, sliced per source) are not part of what the Winograd form was measured on."""
+    _winograd_hold[0] += 1
+    try:
+        yield
+    finally:
+        _winograd_hold[0] -= 1
+
+
+def winograd_weights(weight):
+    """U = G g G^T of Winograd F(2x2, 3x3) (include/vsx.h: vsx_conv3x3_winograd_f16) from a [Cout, 3, 3, C] weight: fp32
+    arithmetic on the fp16 values, rounded to fp16 once, laid out [16, Cout, C] (xi = 4 a + b outermost: sixteen K-major
+    GEMM operands).  16 / 9 of the weight's bytes.  Cached per weight exactly as `subpixel_weights`: stamped with the
+    weight's address and version, dropped with the weight."""
+    import weakref
+    key = id(weight)
+    stamp = (weight.data_ptr(), weight._version)
+    hit = _winograd_cache.get(key)
+    if hit is None or hit[0] != stamp or hit[1]() is not weight:
+        with torch.no_grad():
+            w = weight.detach().float()                                   # [Cout, 3, 3, C]
+            G = torch.tensor(_WINO_G, dtype=torch.float32, device=w.device)
+            u = torch.einsum('ar,orsc,bs->aboc', G, w, G)      # [4, 4, Cout, C]
+            out = u.reshape(16, w.shape[0], w.shape[3]).to(_F16).contiguous()
+        fresh = hit is None or hit[1]() is not weight
+        hit = (stamp, weakref.ref(weight), out)
+        _winograd_cache[key] = hit
+        if fresh:
+            weakref.finalize(weight, _winograd_cache.pop, key, None)
+    return hit[2]
+
+
+def _winograd_supported(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
+    """Mirrors csrc/winograd.hip: wino_supported for the descriptions `conv2d` builds."""
+    if ks != 3 or stride != 1 or upsample or (padding is not None and tuple(padding) != (1, 1)):
+        return False
+    if H <= 0 or W <= 0 or H % 2 or W % 2 or nimg <= 0:
+        return False
+    if C1 <= 0 or C1 % 8 or C2 % 8 or Cout <= 0 or Cout % 8 or (C2 and (C1 % 64 or C2 % 64)):
+        return False
+    M = nimg * H * W
+    return M * Cout < 2 ** 31 and M * (C1 + C2) < 2 ** 31
+
+
+def _winograd_eligible(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
+    """Mirrors vsx_conv3x3_winograd_auto: the form runs where it is supported and measured faster than the direct kernels
+    (profiles/winograd_ab.txt: the 16 x 16 and 8 x 8 levels from 640 input channels, the 32 x 32 level from 1280), and stays
+    out of the way when a test or tool forces a GEMM back end."""
+    mode = _options.get('conv_winograd', 1)
+    if mode == 0 or _winograd_hold[0] or not _winograd_supported(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
+        return False
+    if mode >= 2:
+        return True
+    if _options.get('gemm_pp', 1) != 1 or _options.get('tile_tune', 0) != 0:
+        return False
+    return (C1 + C2 >= 640 and H * W <= 256) or (C1 + C2 >= 1280 and H * W <= 1024)
+
+
+def _conv_winograd(d, weight, device):
+    """The launch behind `conv2d` once the form is chosen: d is the direct path's description, complete."""
+    lib = _lib.load()
+    u = winograd_weights(weight)
+    need = int(lib.vsx_conv3x3_winograd_workspace(ctypes.byref(d)))
+    if need <= 0:
+        raise _lib.VsxError('conv2d: the Winograd form does not take this convolution')
+    ws = torch.empty(need // 2, dtype=_F16, device=device)     # V + Mt: the caching allocator's (under capture: the graph pool's)
+    if FlopCounter.enabled:
+        executed = 2.0 * d.M * d.N * (d.K // 9) * 4               # 16 products per 2 x 2 tile = 4 per output pixel
+        FlopCounter.gemm += executed
+        FlopCounter.gemm_saved += 2.0 * d.M * d.N * d.K - executed
+    if _gemm_log is not None:
+        _gemm_log.write(f'{d.M // 4} {d.N} {d.K // 9} 16 0 0 0 0 0 0 0 0 0 0 0 0 0\n')
+        _gemm_log.flush()
+    check(lib.vsx_conv3x3_winograd_f16(ctypes.byref(d), _p(u), _p(ws), need, _stream()), 'vsx_conv3x3_winograd_f16')
+
+
 def conv2d(x, weight, bias=None, *, x2=None, stride=1, upsample=False, rowvec=None, rows_per_vec=0,
            residual=None, padding=None):
     """Channels-last conv as implicit GEMM.
@@ -438,6 +525,9 @@ def conv2d(x, weight, bias=None, *, x2=None, stride=1, upsample=False, rowvec=No
             raise _lib.VsxError('conv2d: residual shape mismatch')
         d.residual = residual.data_ptr(); d.ldr = Cout
     d.alpha = 1.0
+    if _winograd_eligible(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
+        _conv_winograd(d, weight, x.device)
+        return out
     gemm(d)
     return out
 
@@ -914,12 +1004,13 @@ def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None
     return edit, fg, bg, relevant
 
 
-_options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0'))}
+_options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0')),
+            'conv_winograd': int(os.environ.get('VSX_CONV_WINOGRAD', '1'))}
 
 
 def set_option(name, value):
     """Process-wide tuning / test switch of libvsx (see include/vsx.h: "gemm_pp", "pp_sched", "tile_tune").  The values are
-    mirrored here for the host-side choices that depend on them (`_subpixel_eligible`)."""
+    mirrored here for the host-side choices that depend on them (`_subpixel_eligible`, `_winograd_eligible`)."""
     check(_lib.load().vsx_set_option(name.encode(), int(value)), 'vsx_set_option')
     _options[name] = int(value)
 
