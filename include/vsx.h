@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 14
+#define VSX_ABI_VERSION 15
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -52,6 +52,9 @@ const char* vsx_source_digest(void);
  * "tile_tune" (diagnostics, tools/small_m_sweep.py) forces a tile / ring depth / K-slice count of the workgroup-per-tile kernels.
  * "conv_winograd" = 0 never / 1 default / 2 always-when-supported: what vsx_conv3x3_winograd_auto answers (below). */
 int vsx_set_option(const char* name, int64_t value);
+/* ABI 15: the current value of an option (its environment variable's, or the default, until vsx_set_option); an unknown name fails
+ * like vsx_set_option. */
+int vsx_get_option(const char* name, int64_t* value);
 
 /* ------------------------------------------------------------------------------------------
  * K1/K2: MFMA GEMM / implicit-GEMM convolution with fused epilogues.
@@ -135,6 +138,10 @@ typedef struct vsx_gemm_desc {
 } vsx_gemm_desc;
 
 int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream);
+/* ABI 15: the status vsx_gemm_f16(d, stream) would return under the current options (the same checks and the same plan: one piece of
+   code), without launching anything and without touching the memory d points at.  A caller that can describe a launch in two forms asks
+   before it builds what only one of them needs (videoswap_amd.ops.conv2d: upsample = 2, else the nine-tap form). */
+int vsx_gemm_check(const vsx_gemm_desc* d);
 /* parts per row the launch described by d would write into d->rowstats (see above); the answer does not depend on
    d->rowstats / d->rowstats_parts themselves */
 int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d);

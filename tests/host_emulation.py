@@ -360,8 +360,15 @@ def gemm(desc):
     raise RuntimeError('host emulation: raw vsx_gemm_f16 descriptors are not emulated (call the typed ops)')
 
 
+_option_values = {}
+
+
 def set_option(name, value):
-    pass
+    _option_values[name] = int(value)
+
+
+def get_option(name):
+    return _option_values.get(name, 0)
 
 
 def prof_pause(paused):
@@ -370,7 +377,7 @@ def prof_pause(paused):
 
 _NAMES = ['linear', 'linear_vt', 'conv2d', 'attention_scores', 'softmax_rows', 'head_scores', 'attention_pv', 'attention',
           'temporal_attention', 'group_norm', 'layer_norm', 'silu', 'quick_gelu', 'axpy', 'pack_latents',
-          'unpack_latents', 'cfg_ddim_step', 'masked_blend', 'adapter_scatter', 'gemm', 'set_option', 'prof_pause',
+          'unpack_latents', 'cfg_ddim_step', 'masked_blend', 'adapter_scatter', 'gemm', 'set_option', 'get_option', 'prof_pause',
           'geglu_fwd', 'geglu_bwd', 'silu_bwd', 'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2',
           'adapter_gather', 'attention_lse', 'attention_bwd', 'attention_bwd_supported']
 

@@ -354,6 +354,19 @@ def test_persistent_conv(nimg, H, W, C1, C2, Cout, ks, stride, ups, sched, adden
         assert rel_err(old, ref) < 2e-3
 
 
+def _conv2d_and_its_form(*args, **kwargs):
+    """conv2d's result and the form it was launched in ('subpixel' | 'winograd' | 'direct': what ops._conv_form answered)"""
+    o = ops()
+    real, forms = o._conv_form, []
+    o._conv_form = lambda d: (forms.append(real(d)), forms[-1])[1]
+    try:
+        out = o.conv2d(*args, **kwargs)
+    finally:
+        o._conv_form = real
+    assert len(forms) == 1
+    return out, forms[0]
+
+
 @pytest.mark.parametrize('nimg,Hs,Ws,C,Cout', [
     (32, 32, 32, 640, 640),        # Upsample3D 32 -> 64 at B = 2 (the 896-us launch of a forward)
     (16, 16, 16, 1280, 1280),      # 16 -> 32 at B = 1
@@ -374,9 +387,9 @@ def test_subpixel_form_of_the_nearest_2x_convolution(nimg, Hs, Ws, C, Cout):
     assert torch.allclose(w4[0, :, 1, 1], wf[:, 1:, 1:].sum((1, 2)), atol=2e-3, rtol=2e-3)          # ... and the 2x2 block
     assert torch.allclose(w4[3, :, 1, 1], wf[:, :2, :2].sum((1, 2)), atol=2e-3, rtol=2e-3)          # class (1, 1)
     assert float(w4[0, :, 2].abs().max()) == 0 and float(w4[3, :, 0].abs().max()) == 0               # taps no class reads
-    eligible = o._subpixel_eligible(nimg, Hs, Ws, C, Cout, 3, 1, None, None, None, None)
+    sub, form = _conv2d_and_its_form(x, w, b, upsample=True)
+    eligible = form == 'subpixel'
     assert eligible == (nimg * Hs * Ws >= 4096)
-    sub = o.conv2d(x, w, b, upsample=True)
     o.CONV_SUBPIXEL = False
     try:
         nine = o.conv2d(x, w, b, upsample=True)
@@ -389,6 +402,34 @@ def test_subpixel_form_of_the_nearest_2x_convolution(nimg, Hs, Ws, C, Cout):
         assert rel_err(sub, nine.float(), l2_tol=6e-4, row_tol=3e-3) < 4e-3
     else:
         assert torch.equal(sub, nine)
+
+
+def test_nearest_2x_convolution_the_persistent_kernel_refuses_runs_as_nine_taps():
+    """The library chooses the form (vsx_gemm_check): at the smallest shape the sub-pixel form takes at 1280 columns (48 row
+    tiles x 4 column tiles = 192), a bias that is 8- but not 16-byte aligned — which the persistent kernel does not take — gives
+    the nine-tap result instead of an error; the same values in an aligned bias give the sub-pixel form."""
+    nimg, Hs, Ws, C, Cout = 3, 32, 32, 64, 1280
+    x = rnd(nimg, Hs, Ws, C, seed=170)
+    w, buf = rnd(Cout, 3, 3, C, seed=171, scale=(9 * C) ** -0.5), rnd(Cout + 8, seed=172)
+    b8 = buf[4:4 + Cout]
+    assert b8.data_ptr() % 16 == 8 and b8.is_contiguous()
+    o = ops()
+    ref = conv_ref(x, w, b8, 1, None, True)
+    out8, form8 = _conv2d_and_its_form(x, w, b8, upsample=True)
+    b16 = b8.clone()
+    assert b16.data_ptr() % 16 == 0
+    sub, form16 = _conv2d_and_its_form(x, w, b16, upsample=True)
+    o.CONV_SUBPIXEL = False
+    try:
+        nine = o.conv2d(x, w, b8, upsample=True)
+    finally:
+        o.CONV_SUBPIXEL = True
+    assert form8 == 'direct' and form16 == 'subpixel'
+    assert torch.equal(out8, nine)
+    assert rel_err(out8, ref) < 2e-3
+    assert rel_err(sub, ref) < 2e-3
+    assert not torch.equal(sub, nine)
+    assert rel_err(sub, nine.float(), l2_tol=6e-4, row_tol=3e-3) < 4e-3
 
 
 @pytest.mark.parametrize('M,N,K,res', [(65536, 320, 320, True), (65536, 320, 320, False), (16384, 640, 640, True),

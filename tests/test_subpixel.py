@@ -1,9 +1,11 @@
 """Host side of the sub-pixel form of the nearest-2x convolution (include/vsx.h: vsx_gemm_desc.upsample = 2; reference:
 Upsample3D, /root/reference/videoswap/models/animatediff_models/resnet.py:54,66 = F.interpolate(scale_factor=2, mode="nearest")
-followed by a 3x3 convolution).  No GPU: the combined weights against their definition, the cache, the eligibility rule."""
+followed by a 3x3 convolution).  No GPU: the combined weights against their definition, the cache, and which convolutions take the form (the library's answer,
+through the function `conv2d` itself asks)."""
 import torch
 import torch.nn.functional as F
 
+from test_winograd import _desc
 from videoswap_amd import ops
 
 
@@ -54,9 +56,17 @@ def test_subpixel_weights_are_cached_per_weight_version():
     assert key not in ops._subpixel_cache               # the entry lives exactly as long as its weight
 
 
-def test_subpixel_eligibility_mirrors_the_library_rule(monkeypatch):
-    ok = lambda nimg, hs, ws, c, o, **kw: ops._subpixel_eligible(nimg, hs, ws, c, o, kw.get('ks', 3), kw.get('stride', 1),  # noqa: E731
-                                                                 kw.get('x2'), kw.get('rowvec'), kw.get('residual'), kw.get('padding'))
+def _takes_subpixel(nimg, hs, ws, c, o, ks=3, stride=1, residual=None, padding=None, bias=20480):
+    """the form `conv2d` takes for this nearest-2x convolution, asked of the library on a description with made-up aligned
+    pointers (nothing is launched, nothing they point at is read)"""
+    d = _desc(nimg, 2 * hs, 2 * ws, c, 0, o, ks=ks, stride=stride, upsample=1, padding=padding)
+    d.bias, d.residual, d.ldr = bias, residual, o
+    return ops._conv_form(d) == 'subpixel'
+
+
+def test_subpixel_form_is_the_librarys_choice(monkeypatch):
+    ok = _takes_subpixel
+    saved = {name: ops.get_option(name) for name in ('gemm_pp', 'tile_tune')}
     assert ok(32, 32, 32, 640, 640) and ok(16, 16, 16, 1280, 1280)           # the UNet's 32 -> 64 and 16 -> 32 at B = 2 / 1
     assert ok(16, 14, 24, 1280, 1280)                                         # the 448 x 768 clip
     assert not ok(32, 8, 8, 1280, 1280)                                       # too few tiles for the persistent kernel
@@ -64,12 +74,19 @@ def test_subpixel_eligibility_mirrors_the_library_rule(monkeypatch):
     assert not ok(32, 32, 32, 72, 640)                                        # a K slab would straddle taps
     assert not ok(3, 30, 30, 640, 640)                                        # rows per class not a multiple of the tile
     assert not ok(32, 32, 32, 640, 640, stride=2) and not ok(32, 32, 32, 640, 640, ks=1)
-    assert not ok(32, 32, 32, 640, 640, residual=object()) and not ok(32, 32, 32, 640, 640, padding=(0, 1))
-    monkeypatch.setitem(ops._options, 'gemm_pp', 0)                           # tests / A-B runs switch the persistent kernel off
-    assert not ok(32, 32, 32, 640, 640)
-    monkeypatch.setitem(ops._options, 'gemm_pp', 1)
-    monkeypatch.setitem(ops._options, 'tile_tune', 2)                         # ... or force a tile
-    assert not ok(32, 32, 32, 640, 640)
-    monkeypatch.setitem(ops._options, 'tile_tune', 0)
+    assert not ok(32, 32, 32, 640, 640, residual=24576) and not ok(32, 32, 32, 640, 640, padding=(0, 1))
+    # the smallest launch the form takes at 1280 columns (48 row tiles x 4 column tiles = 192) — and the persistent kernel wants a
+    # 16-byte aligned bias: one that is only 8-byte aligned takes the nine-tap form instead of failing
+    assert ok(3, 32, 32, 64, 1280) and not ok(3, 32, 32, 64, 1280, bias=20480 + 8)
+    try:
+        ops.set_option('gemm_pp', 0)                                          # tests / A-B runs switch the persistent kernel off
+        assert not ok(32, 32, 32, 640, 640)
+        ops.set_option('gemm_pp', 1)
+        ops.set_option('tile_tune', 2)                                        # ... or force a tile
+        assert not ok(32, 32, 32, 640, 640)
+    finally:
+        for name, value in saved.items():
+            ops.set_option(name, value)
+    assert ok(32, 32, 32, 640, 640)
     monkeypatch.setattr(ops, 'CONV_SUBPIXEL', False)
     assert not ok(32, 32, 32, 640, 640)

@@ -1,6 +1,7 @@
 """Host side of the Winograd F(2x2, 3x3) form of the stride-1 3x3 convolutions (include/vsx.h: vsx_conv3x3_winograd_f16;
 csrc/winograd.hip).  No GPU: a torch restatement of the three stages with the kernels' rounding points against F.conv2d in
-fp64, the eligibility mirror against the library's own function on both sides of every threshold, and the weight cache."""
+fp64, where `conv2d` takes the form (the library's rule, on both sides of every threshold and under every option set), and the
+weight cache."""
 import ctypes
 import gc
 
@@ -91,43 +92,48 @@ CASES = [
 ]
 
 
-def test_eligibility_mirrors_the_library_rule_on_both_sides_of_every_threshold():
+def _takes_winograd(case):
+    return ops._conv_form(_desc(*case)) == 'winograd'
+
+
+def test_the_form_runs_where_the_library_rule_says_on_both_sides_of_every_threshold():
+    """What `conv2d` takes (`ops._conv_form`) under every option set, against the rule as csrc/options.cpp states it."""
     lib = _lib.load()
-    saved = dict(ops._options)
+    names = ('conv_winograd', 'gemm_pp', 'tile_tune')
+    saved = {name: ops.get_option(name) for name in names}
+    supported = []                                       # the rows the form takes at all: a workspace size > 0, by the formula
+    for i, case in enumerate(CASES):
+        nimg, H, W, C1, C2, Cout = case[:6]
+        need = int(lib.vsx_conv3x3_winograd_workspace(ctypes.byref(_desc(*case))))
+        if need:
+            assert need == 16 * (nimg * H * W // 4) * (C1 + C2 + Cout) * 2
+            supported.append(i)
+    assert supported == [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 22, 23]
+    # under the defaults: the enabled set, the rows exactly on a threshold and the written-out padding, nothing else
+    enabled = [0, 1, 2, 4, 7, 9, 22]
+    expect = [({}, enabled), ({'conv_winograd': 0}, []), ({'conv_winograd': 2}, supported),
+              ({'conv_winograd': 2, 'gemm_pp': 0}, supported),
+              ({'gemm_pp': 0}, []), ({'gemm_pp': 2}, []), ({'tile_tune': 2}, [])]      # mode 1 stays out of a forced back end's way
     try:
-        for opts in ({}, {'conv_winograd': 0}, {'conv_winograd': 2}, {'gemm_pp': 0}, {'gemm_pp': 2}, {'tile_tune': 2},
-                     {'conv_winograd': 2, 'gemm_pp': 0}):
-            for name in ('conv_winograd', 'gemm_pp', 'tile_tune'):
+        for opts, want in expect:
+            for name in names:
                 ops.set_option(name, {**{'conv_winograd': 1, 'gemm_pp': 1, 'tile_tune': 0}, **opts}[name])
-            for case in CASES:
-                nimg, H, W, C1, C2, Cout, ks, stride, ups, padding = case
-                d = _desc(*case)
-                native = int(lib.vsx_conv3x3_winograd_auto(ctypes.byref(d)))
-                mirror = ops._winograd_eligible(nimg, H, W, C1, C2, Cout, ks, stride, bool(ups), padding)
-                assert bool(native) == mirror, (opts, case)
-                supported = int(lib.vsx_conv3x3_winograd_workspace(ctypes.byref(d)))
-                assert (supported > 0) == ops._winograd_supported(nimg, H, W, C1, C2, Cout, ks, stride, bool(ups), padding), case
-                if supported:
-                    assert supported == 16 * (nimg * H * W // 4) * (C1 + C2 + Cout) * 2
-        # under the defaults: the enabled set, the rows exactly on a threshold and the written-out padding, nothing else
-        for name, v in (('conv_winograd', 1), ('gemm_pp', 1), ('tile_tune', 0)):
-            ops.set_option(name, v)
-        on = [i for i, c in enumerate(CASES) if ops._winograd_eligible(*c[:8], bool(c[8]), c[9])]
-        assert on == [0, 1, 2, 4, 7, 9, 22]
+            assert [i for i, c in enumerate(CASES) if _takes_winograd(c)] == want, opts
+            assert [i for i, c in enumerate(CASES) if lib.vsx_conv3x3_winograd_auto(ctypes.byref(_desc(*c)))] == want, opts
     finally:
-        for name in ('conv_winograd', 'gemm_pp', 'tile_tune'):
+        for name in names:
             ops.set_option(name, saved[name])
 
 
 def test_the_gradient_path_keeps_the_direct_kernels():
-    args = (*CASES[0][:8], False, None)
-    assert ops._winograd_eligible(*args)
+    case = CASES[0]
+    assert _takes_winograd(case)
     with ops.winograd_suspended():
-        assert not ops._winograd_eligible(*args)
+        assert not _takes_winograd(case)
         with ops.winograd_suspended():
-            assert not ops._winograd_eligible(*args)
-        assert not ops._winograd_eligible(*args)
-    assert ops._winograd_eligible(*args)
+            assert not _takes_winograd(case)
+        assert not _takes_winograd(case)
+    assert _takes_winograd(case)
     import inspect
     from videoswap_amd import autograd
     assert inspect.getsource(autograd._Conv2d).count('winograd_suspended') == 2          # the forward and the dgrad launches

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import winograd_case as wc
+from test_winograd import _desc
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,7 @@ def _conv(ops, c):
 @pytest.fixture
 def ops():
     from videoswap_amd import ops as _ops
-    saved = _ops._options.get('conv_winograd', 1)
+    saved = _ops.get_option('conv_winograd')
     yield _ops
     _ops.set_option('conv_winograd', saved)
 
@@ -51,7 +52,7 @@ def test_winograd_convolution_against_fp32_and_the_direct_kernels(ops, shape):
     c, ref = _case(shape)
     forced = shape[-1]
     ops.set_option('conv_winograd', 2 if forced else 1)
-    assert ops._winograd_eligible(*shape[:6], 3, 1, False, None)
+    assert ops._conv_form(_desc(*shape[:6])) == 'winograd'
     assert forced or shape[3] + shape[4] >= 640          # the unforced shapes take the form under the automatic rule
     launches = []
     real = ops._conv_winograd
@@ -93,7 +94,7 @@ def test_an_unsupported_description_is_refused(ops):
     assert rc == _lib.VSX_E_UNSUPPORTED and b'even' in lib.vsx_last_error()
     # and conv2d itself takes the direct kernels for it, whatever the option says
     ops.set_option('conv_winograd', 2)
-    assert not ops._winograd_eligible(3, 4, 5, 64, 0, 64, 3, 1, False, None)
+    assert ops._conv_form(_desc(3, 4, 5, 64, 0, 64)) == 'direct'
     y = ops.conv2d(x, c['weight'], c['bias'])
     ref = wc.reference(dict(x=x.cpu(), x2=None, weight=c['weight'].cpu(), bias=c['bias'].cpu(), rowvec=None, residual=None),
                        torch.float32)

@@ -375,6 +375,9 @@ static void check_plans() {
         bool ok = rc == VSX_OK && (int)plan.refused == r.refused && plan.stat_parts == r.stat_parts && parts == r.stat_parts &&
                   plan.workspace_bytes == r.workspace_bytes && asked.workspace_bytes == r.workspace_bytes && bytes == r.workspace_bytes &&
                   vsx_gemm_rowstats_parts(&d) == r.stat_parts && plan.splits == r.splits && plan.nk_per == r.nk_per;
+        // what the host asks before it chooses a form: the launch's own status, refused exactly where the plan is
+        const int status = vsx_gemm_check(&d);
+        ok = ok && status == (r.refused ? VSX_E_UNSUPPORTED : VSX_OK);
         if (!r.refused) {
             ok = ok && (int)plan.family == r.family;
             if (r.family == GEMM_TILE)
@@ -390,9 +393,9 @@ static void check_plans() {
         }
         if (!ok) {
             ++bad;
-            printf("  plan of '%s': rc %d family %d tile %dx%d (%d x %d waves) deep %d splits %d x %d slabs, %ld parts (asked: %ld), %lld bytes (asked: %lld), refused %d  FAIL\n",
+            printf("  plan of '%s': rc %d family %d tile %dx%d (%d x %d waves) deep %d splits %d x %d slabs, %ld parts (asked: %ld), %lld bytes (asked: %lld), refused %d, vsx_gemm_check %d  FAIL\n",
                    r.name, rc, (int)plan.family, plan.BM, plan.BN, plan.WAVES_M, plan.WAVES_N, (int)plan.deep, plan.splits, plan.nk_per,
-                   plan.stat_parts, (long)parts, (long long)plan.workspace_bytes, (long long)bytes, (int)plan.refused);
+                   plan.stat_parts, (long)parts, (long long)plan.workspace_bytes, (long long)bytes, (int)plan.refused, status);
         }
     }
     plan_options(PlanRow{"defaults", 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 10, 0});

@@ -1289,14 +1289,13 @@ int run_plan(const GemmPlan& plan, GemmParams& p, hipStream_t stream) {
     return rc;
 }
 
-}  // namespace
-
-extern "C" int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    GemmParams p;
-    int rc = fill_params(d, p);
+// What vsx_gemm_f16 and vsx_gemm_check share: every check of the descriptor, the plan under the current option values, the plan's
+// refusals, and the row statistics and workspace bound into p.  No HIP call, and nothing the descriptor points at is read.
+// VSX_OK with d->M == 0 means "nothing to launch" (p and plan are then not filled).
+int check_and_plan(const vsx_gemm_desc* d, GemmParams& p, GemmPlan& plan) {
+    const int rc = fill_params(d, p);
     if (rc != VSX_OK || d->M == 0) return rc;
-    const GemmPlan plan = plan_gemm(*d, p, false);
+    plan = plan_gemm(*d, p, false);
     VSX_REQUIRE(plan.refused != PLAN_ROWSTATS_PARTS, VSX_E_UNSUPPORTED,
                 "gemm: rowstats with %ld parts, but this launch writes %ld (ask vsx_gemm_rowstats_parts first)",
                 (long)d->rowstats_parts, plan.stat_parts);
@@ -1308,6 +1307,17 @@ extern "C" int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream_) {
         p.rowstats_parts = (int)plan.stat_parts;
     }
     if (plan.forced || plan.splits > 1) p.ws = (float*)d->workspace;
+    return VSX_OK;
+}
+
+}  // namespace
+
+extern "C" int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    GemmParams p;
+    GemmPlan plan;
+    int rc = check_and_plan(d, p, plan);
+    if (rc != VSX_OK || d->M == 0) return rc;
     const long sample = prof_begin(stream);
     if (sample == PROF_FAILED) return VSX_E_LAUNCH;
     rc = run_plan(plan, p, stream);
@@ -1332,4 +1342,12 @@ extern "C" int64_t vsx_gemm_workspace(const vsx_gemm_desc* d) {
     GemmParams p;
     if (!d || d->M <= 0 || fill_params(d, p) != VSX_OK) return 0;
     return plan_gemm(*d, p, true).workspace_bytes;
+}
+
+// The status vsx_gemm_f16(d, ...) would return under the current option values, without launching anything (the caller asks
+// before it builds what only one form of a launch needs: ops.conv2d and the sub-pixel weights).
+extern "C" int vsx_gemm_check(const vsx_gemm_desc* d) {
+    GemmParams p;
+    GemmPlan plan;
+    return check_and_plan(d, p, plan);
 }

@@ -1,5 +1,5 @@
-// The option table of the whole library: vsx_set_option and vsxg::gemm_option (options.h).  An option's initial value comes from its
-// environment variable the first time it is asked for; vsx_set_option overrides it.  Every option is for A/B runs and tests: the
+// The option table of the whole library: vsx_set_option, vsx_get_option and vsxg::gemm_option (options.h).  An option's initial value
+// comes from its environment variable the first time it is asked for; vsx_set_option overrides it.  Every option is for A/B runs and tests: the
 // product path runs on the defaults.
 //
 //   name          environment       default  meaning
@@ -31,7 +31,8 @@
 //                                            320 columns)
 //   conv_winograd VSX_CONV_WINOGRAD 1        Winograd F(2x2, 3x3) form of the stride-1 3x3 convolutions (winograd.hip): 0 = never, 1 = the
 //                                            shapes of vsx_conv3x3_winograd_auto unless a GEMM back end is forced (gemm_pp != 1 or
-//                                            tile_tune != 0), 2 = every supported description (tests)
+//                                            tile_tune != 0), 2 = every supported description (tests).  That function is the one
+//                                            statement of the rule: ops.conv2d asks it for every stride-1 3x3 convolution
 #include "options.h"
 
 #include <stdlib.h>
@@ -71,5 +72,13 @@ extern "C" int vsx_set_option(const char* name, int64_t value) {
     auto* o = name ? vsxg::find_option(name) : nullptr;
     if (!o) return vsx_fail(VSX_E_BADSHAPE, "vsx_set_option: unknown option '%s'", name ? name : "(null)");
     o->value = (long)value;
+    return VSX_OK;
+}
+
+extern "C" int vsx_get_option(const char* name, int64_t* value) {
+    auto* o = name ? vsxg::find_option(name) : nullptr;
+    if (!o) return vsx_fail(VSX_E_BADSHAPE, "vsx_get_option: unknown option '%s'", name ? name : "(null)");
+    VSX_REQUIRE(value != nullptr, VSX_E_BADSHAPE, "vsx_get_option: null value pointer");
+    *value = o->value;
     return VSX_OK;
 }

@@ -188,7 +188,7 @@ extern "C" int64_t vsx_conv3x3_winograd_workspace(const vsx_gemm_desc* d) {
 
 // The choice under option "conv_winograd" = 1 (auto): the shapes where the three launches measured faster than the direct
 // kernels at one and at two clips per step by more than either's spread (profiles/winograd_ab.txt: the 16 x 16 and 8 x 8 levels
-// from 640 input channels, the 32 x 32 level from 1280), and no forced back end.  videoswap_amd.ops._winograd_eligible mirrors it.
+// from 640 input channels, the 32 x 32 level from 1280), and no forced back end.  The only statement of the rule: videoswap_amd.ops.conv2d asks here.
 extern "C" int64_t vsx_conv3x3_winograd_auto(const vsx_gemm_desc* d) {
     const char* why;
     const long mode = vsxg::gemm_option("conv_winograd");

@@ -7,6 +7,7 @@ returns the output tensor.  There is no fallback implementation.
 import contextlib
 import ctypes
 import os
+import weakref
 
 import torch
 
@@ -181,7 +182,28 @@ class DeferredLN:
         return y.view(self.x.shape)
 
 
-_fold_cache = {}      # (id(weight), id(gamma)) -> (stamp, weight ref, W o gamma, c1, c2, {pe products}, gamma ref)
+# Operands derived from a weight, one protocol (`_derived`): key -> (stamp, weak references to the owners, *derived values)
+_fold_cache = {}          # (id(weight), id(gamma)) -> (.., .., W o gamma, c1, c2, {pe products})
+_subpixel_cache = {}      # id(weight) -> (.., .., [4, Cout, 3, 3, C] fp16)
+_winograd_cache = {}      # id(weight) -> (.., .., [16, Cout, C] fp16)
+
+
+def _derived(cache, key, owners, stamped, build):
+    """cache[key], rebuilt (`build()` -> the derived values, under no_grad) when the address or version of a tensor in
+    `stamped` has changed (LoRA merge / load_state_dict bump the version) or another object has taken the id of one of
+    `owners`.  An entry lives exactly as long as owners[0], its weight tensor (a finalizer on the weight, registered once per
+    weight object, evicts it: the fused-projection tensors that a LoRA merge rebuilds do not leave stale copies behind, and
+    nothing is ever dropped while its weight — and therefore a graph captured over it — can still be used)."""
+    stamp = tuple((t.data_ptr(), t._version) for t in stamped)
+    hit = cache.get(key)
+    if hit is None or hit[0] != stamp or any(r() is not o for r, o in zip(hit[1], owners)):
+        fresh = hit is None or hit[1][0]() is not owners[0]
+        with torch.no_grad():
+            hit = (stamp, tuple(weakref.ref(o) for o in owners), *build())
+        cache[key] = hit
+        if fresh:
+            weakref.finalize(owners[0], cache.pop, key, None)
+    return hit
 
 
 def fold_cache_tensors():
@@ -197,30 +219,18 @@ def fold_cache_tensors():
 
 
 def _ln_folded(weight, bias, ln):
-    """W' = W o gamma (fp16, the B operand), c1[n] = sum_k W'[n, k] (fp32), c2 = beta W^T + b (fp16, the epilogue bias);
-    rebuilt when any of the parameters changes (LoRA merge / load_state_dict bump the version).  An entry lives exactly as
-    long as its weight tensor (a finalizer on the weight evicts it: the fused-projection tensors that a LoRA merge
-    rebuilds do not leave stale folded copies behind, and nothing is ever dropped while its weight — and therefore a
-    graph captured over it — can still be used)."""
-    import weakref
-    key = (id(weight), id(ln.gamma))
-    stamp = tuple((t.data_ptr(), t._version) for t in (weight, ln.gamma, ln.beta) + ((bias,) if bias is not None else ()))
-    hit = _fold_cache.get(key)
-    if hit is None or hit[0] != stamp or hit[1]() is not weight or hit[6]() is not ln.gamma:
-        with torch.no_grad():
-            w32 = weight.detach().reshape(weight.shape[0], -1).float()
-            wf = (w32 * ln.gamma.detach().float()[None, :]).to(_F16).contiguous()
-            c1 = wf.float().sum(1).contiguous()
-            c2 = w32 @ ln.beta.detach().float()
-            if bias is not None:
-                c2 = c2 + bias.detach().float()
-            c2 = c2.to(_F16).contiguous()
-        fresh = hit is None or hit[1]() is not weight
-        hit = (stamp, weakref.ref(weight), wf, c1, c2, {}, weakref.ref(ln.gamma))
-        _fold_cache[key] = hit
-        if fresh:
-            weakref.finalize(weight, _fold_cache.pop, key, None)
-    return hit
+    """W' = W o gamma (fp16, the B operand), c1[n] = sum_k W'[n, k] (fp32), c2 = beta W^T + b (fp16, the epilogue bias) as
+    entry[2], [3], [4] of `_fold_cache`; rebuilt when any of the parameters changes."""
+    def build():
+        w32 = weight.detach().reshape(weight.shape[0], -1).float()
+        wf = (w32 * ln.gamma.detach().float()[None, :]).to(_F16).contiguous()
+        c1 = wf.float().sum(1).contiguous()
+        c2 = w32 @ ln.beta.detach().float()
+        if bias is not None:
+            c2 = c2 + bias.detach().float()
+        return wf, c1, c2.to(_F16).contiguous(), {}
+    return _derived(_fold_cache, (id(weight), id(ln.gamma)), (weight, ln.gamma),
+                    (weight, ln.gamma, ln.beta) + ((bias,) if bias is not None else ()), build)
 
 
 def _ln_pe_rows(hit, weight, ln, M):
@@ -239,6 +249,20 @@ def _ln_pe_rows(hit, weight, ln, M):
             hit[5].clear()
         hit[5][key] = rv
     return rv, ln.rows_per_frame
+
+
+def _bind_folded_ln(d, weight, bias, ln):
+    """The LayerNorm `ln` applied inside the launch d describes: the folded weight and bias, the row statistics and c1, and the
+    positional-encoding rows where there are any.  Returns what the caller keeps alive until the launch is enqueued."""
+    hit = _ln_folded(weight, bias, ln)
+    rv, rpv = _ln_pe_rows(hit, weight, ln, d.M)
+    st = ln.stats()
+    d.B = hit[2].data_ptr()
+    d.bias = hit[4].data_ptr()
+    d.rowscale, d.colvec = st.data_ptr(), hit[3].data_ptr()
+    if rv is not None:
+        d.rowvec, d.rows_per_vec = rv.data_ptr(), rpv
+    return hit, rv, st
 
 
 def linear(x, weight, bias=None, residual=None, geglu=False, out=None, row_stats=False):
@@ -272,17 +296,9 @@ def linear(x, weight, bias=None, residual=None, geglu=False, out=None, row_stats
     d.bias = bias.data_ptr() if bias is not None else None
     keep = None
     if ln is not None:
-        hit = _ln_folded(weight, bias, ln)
-        rv, rpv = _ln_pe_rows(hit, weight, ln, M)
-        if rv is not None and geglu:
+        if ln.pe is not None and geglu:
             raise _lib.VsxError('linear: a positional encoding cannot be folded into a GEGLU projection')
-        st = ln.stats()
-        keep = (hit, rv, st)
-        d.B = hit[2].data_ptr()
-        d.bias = hit[4].data_ptr()
-        d.rowscale, d.colvec = st.data_ptr(), hit[3].data_ptr()
-        if rv is not None:
-            d.rowvec, d.rows_per_vec = rv.data_ptr(), rpv
+        keep = _bind_folded_ln(d, weight, bias, ln)
     if residual is not None:
         if residual.numel() != M * N:
             raise _lib.VsxError('linear: residual shape mismatch')
@@ -333,12 +349,7 @@ def linear_vt(x, weight, bias, rows_per_img, ldvt=None):
     if ln is not None:
         if ln.pe is not None:
             raise _lib.VsxError('linear_vt: a positional encoding cannot be folded into the transposed V projection')
-        hit = _ln_folded(weight, bias, ln)
-        st = ln.stats()
-        keep = (hit, st)
-        d.B = hit[2].data_ptr()
-        d.bias = hit[4].data_ptr()
-        d.rowscale, d.colvec = st.data_ptr(), hit[3].data_ptr()
+        keep = _bind_folded_ln(d, weight, bias, ln)
     d.alpha = 1.0
     gemm(d)
     del keep
@@ -347,7 +358,6 @@ def linear_vt(x, weight, bias, rows_per_img, ldvt=None):
 
 # VSX_CONV_SUBPIXEL=0: the nearest-2x convolutions always as nine taps on the upsampled image (A/B runs)
 CONV_SUBPIXEL = os.environ.get('VSX_CONV_SUBPIXEL', '1') != '0'
-_subpixel_cache = {}      # id(weight) -> (stamp, weight ref, [4, Cout, 3, 3, C] fp16)
 
 
 def subpixel_weights(weight):
@@ -358,44 +368,21 @@ def subpixel_weights(weight):
     and the same along the columns.  Returns [4, Cout, 3, 3, C] (class = 2 ph + pw): the four taps of class (ph, pw) sit at
     window positions (ph.., pw..) of a plain pad-1 3x3 window on the source, the other five are zero and never read
     (include/vsx.h: vsx_gemm_desc.upsample = 2).  4 / 9 of the multiplications of the nine-tap form.  Cached per weight."""
-    import weakref
-    key = id(weight)
-    stamp = (weight.data_ptr(), weight._version)
-    hit = _subpixel_cache.get(key)
-    if hit is None or hit[0] != stamp or hit[1]() is not weight:
-        with torch.no_grad():
-            w = weight.detach().float()                                   # [Cout, 3, 3, C]
-            rows = {0: ((0, (0,)), (1, (1, 2))), 1: ((1, (0, 1)), (2, (2,)))}      # parity -> ((window tap, filter taps), ...)
-            out = torch.zeros(4, *w.shape, dtype=torch.float32, device=w.device)
-            for ph in (0, 1):
-                for pw in (0, 1):
-                    for th, fh in rows[ph]:
-                        for tw, fw in rows[pw]:
-                            out[2 * ph + pw, :, th, tw] = sum(w[:, a, b] for a in fh for b in fw)
-            out = out.to(_F16).contiguous()
-        fresh = hit is None or hit[1]() is not weight
-        hit = (stamp, weakref.ref(weight), out)
-        _subpixel_cache[key] = hit
-        if fresh:
-            weakref.finalize(weight, _subpixel_cache.pop, key, None)
-    return hit[2]
-
-
-def _subpixel_eligible(nimg, Hs, Ws, C1, Cout, ks, stride, x2, rowvec, residual, padding):
-    """Mirrors the library's own conditions (gemm.hip: upsample == 2): bias-only single-source 3x3, and a launch the
-    persistent kernel's 256-row tiles take (enough tiles, whole tiles per class)."""
-    if not CONV_SUBPIXEL or ks != 3 or stride != 1 or x2 is not None or rowvec is not None or residual is not None \
-            or padding is not None or C1 % 64 or Cout % 320:
-        return False
-    if _options.get('gemm_pp', 1) not in (1, 2) or _options.get('tile_tune', 0) != 0:
-        return False                    # the persistent kernel is switched off / a tile or a K split is forced (A/B runs, tests)
-    mc = nimg * Hs * Ws
-    return mc % 256 == 0 and (4 * mc // 256) * (Cout // 320) >= 192
+    def build():
+        w = weight.detach().float()                                   # [Cout, 3, 3, C]
+        rows = {0: ((0, (0,)), (1, (1, 2))), 1: ((1, (0, 1)), (2, (2,)))}      # parity -> ((window tap, filter taps), ...)
+        out = torch.zeros(4, *w.shape, dtype=torch.float32, device=w.device)
+        for ph in (0, 1):
+            for pw in (0, 1):
+                for th, fh in rows[ph]:
+                    for tw, fw in rows[pw]:
+                        out[2 * ph + pw, :, th, tw] = sum(w[:, a, b] for a in fh for b in fw)
+        return (out.to(_F16).contiguous(),)
+    return _derived(_subpixel_cache, id(weight), (weight,), (weight,), build)[2]
 
 
 # VSX_CONV_WINOGRAD (library option "conv_winograd"): 0 = the stride-1 3x3 convolutions always on the direct kernels,
-# 1 = Winograd F(2x2, 3x3) where it measured faster (`_winograd_eligible`), 2 = wherever the form is supported (tests)
-_winograd_cache = {}      # id(weight) -> (stamp, weight ref, [16, Cout, C] fp16)
+# 1 = Winograd F(2x2, 3x3) where it measured faster (vsx_conv3x3_winograd_auto), 2 = wherever the form is supported (tests)
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 _winograd_hold = [0]      # > 0: the gradient path is calling (videoswap_amd/autograd.py) — the training step keeps the direct kernels
 
@@ -414,50 +401,30 @@ def winograd_suspended():
 def winograd_weights(weight):
     """U = G g G^T of Winograd F(2x2, 3x3) (include/vsx.h: vsx_conv3x3_winograd_f16) from a [Cout, 3, 3, C] weight: fp32
     arithmetic on the fp16 values, rounded to fp16 once, laid out [16, Cout, C] (xi = 4 a + b outermost: sixteen K-major
-    GEMM operands).  16 / 9 of the weight's bytes.  Cached per weight exactly as `subpixel_weights`: stamped with the
-    weight's address and version, dropped with the weight."""
-    import weakref
-    key = id(weight)
-    stamp = (weight.data_ptr(), weight._version)
-    hit = _winograd_cache.get(key)
-    if hit is None or hit[0] != stamp or hit[1]() is not weight:
-        with torch.no_grad():
-            w = weight.detach().float()                                   # [Cout, 3, 3, C]
-            G = torch.tensor(_WINO_G, dtype=torch.float32, device=w.device)
-            u = torch.einsum('ar,orsc,bs->aboc', G, w, G)      # [4, 4, Cout, C]
-            out = u.reshape(16, w.shape[0], w.shape[3]).to(_F16).contiguous()
-        fresh = hit is None or hit[1]() is not weight
-        hit = (stamp, weakref.ref(weight), out)
-        _winograd_cache[key] = hit
-        if fresh:
-            weakref.finalize(weight, _winograd_cache.pop, key, None)
-    return hit[2]
+    GEMM operands).  16 / 9 of the weight's bytes.  Cached per weight."""
+    def build():
+        w = weight.detach().float()                                   # [Cout, 3, 3, C]
+        G = torch.tensor(_WINO_G, dtype=torch.float32, device=w.device)
+        u = torch.einsum('ar,orsc,bs->aboc', G, w, G)      # [4, 4, Cout, C]
+        return (u.reshape(16, w.shape[0], w.shape[3]).to(_F16).contiguous(),)
+    return _derived(_winograd_cache, id(weight), (weight,), (weight,), build)[2]
 
 
-def _winograd_supported(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
-    """Mirrors csrc/winograd.hip: wino_supported for the descriptions `conv2d` builds."""
-    if ks != 3 or stride != 1 or upsample or (padding is not None and tuple(padding) != (1, 1)):
-        return False
-    if H <= 0 or W <= 0 or H % 2 or W % 2 or nimg <= 0:
-        return False
-    if C1 <= 0 or C1 % 8 or C2 % 8 or Cout <= 0 or Cout % 8 or (C2 and (C1 % 64 or C2 % 64)):
-        return False
-    M = nimg * H * W
-    return M * Cout < 2 ** 31 and M * (C1 + C2) < 2 ** 31
-
-
-def _winograd_eligible(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
-    """Mirrors vsx_conv3x3_winograd_auto: the form runs where it is supported and measured faster than the direct kernels
-    (profiles/winograd_ab.txt: the 16 x 16 and 8 x 8 levels from 640 input channels, the 32 x 32 level from 1280), and stays
-    out of the way when a test or tool forces a GEMM back end."""
-    mode = _options.get('conv_winograd', 1)
-    if mode == 0 or _winograd_hold[0] or not _winograd_supported(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
-        return False
-    if mode >= 2:
-        return True
-    if _options.get('gemm_pp', 1) != 1 or _options.get('tile_tune', 0) != 0:
-        return False
-    return (C1 + C2 >= 640 and H * W <= 256) or (C1 + C2 >= 1280 and H * W <= 1024)
+def _conv_form(d):
+    """'subpixel' | 'winograd' | 'direct': the form `conv2d` launches the complete description d in.  The library decides, under
+    its current options: the sub-pixel form of a nearest-2x convolution where vsx_gemm_f16 would take it (d.upsample is then
+    left at 2), the Winograd form where vsx_conv3x3_winograd_auto says so and the gradient path is not calling.  The
+    conditions in front of the first question only spare a call that cannot pass (the library checks them too)."""
+    lib = _lib.load()
+    if d.upsample and CONV_SUBPIXEL and d.ks == 3 and d.stride == 1 and d.pad_lo < 0 and d.pad_hi < 0 \
+            and not (d.A2 or d.rowvec or d.residual):
+        d.upsample = 2
+        if lib.vsx_gemm_check(ctypes.byref(d)) == 0:
+            return 'subpixel'
+        d.upsample = 1
+    if _winograd_hold[0] == 0 and lib.vsx_conv3x3_winograd_auto(ctypes.byref(d)) == 1:
+        return 'winograd'
+    return 'direct'
 
 
 def _conv_winograd(d, weight, device):
@@ -511,13 +478,6 @@ def conv2d(x, weight, bias=None, *, x2=None, stride=1, upsample=False, rowvec=No
     d.B = weight.data_ptr(); d.ldb = d.K
     d.C = out.data_ptr(); d.ldc = Cout
     d.bias = bias.data_ptr() if bias is not None else None
-    if upsample and _subpixel_eligible(nimg, Hs, Ws, C1, Cout, ks, stride, x2, rowvec, residual, padding):
-        w4 = subpixel_weights(weight)
-        d.upsample = 2
-        d.B = w4.data_ptr()
-        d.alpha = 1.0
-        gemm(d, k_flop=4 * C1)
-        return out
     if rowvec is not None:
         d.rowvec = rowvec.data_ptr(); d.rows_per_vec = rows_per_vec
     if residual is not None:
@@ -525,10 +485,15 @@ def conv2d(x, weight, bias=None, *, x2=None, stride=1, upsample=False, rowvec=No
             raise _lib.VsxError('conv2d: residual shape mismatch')
         d.residual = residual.data_ptr(); d.ldr = Cout
     d.alpha = 1.0
-    if _winograd_eligible(nimg, H, W, C1, C2, Cout, ks, stride, upsample, padding):
+    form = _conv_form(d)
+    if form == 'subpixel':
+        w4 = subpixel_weights(weight)
+        d.B = w4.data_ptr()
+        gemm(d, k_flop=4 * C1)
+    elif form == 'winograd':
         _conv_winograd(d, weight, x.device)
-        return out
-    gemm(d)
+    else:
+        gemm(d)
     return out
 
 
@@ -1004,15 +969,17 @@ def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None
     return edit, fg, bg, relevant
 
 
-_options = {'gemm_pp': int(os.environ.get('VSX_GEMM_PP', '1')), 'tile_tune': int(os.environ.get('VSX_TUNE_TILE', '0')),
-            'conv_winograd': int(os.environ.get('VSX_CONV_WINOGRAD', '1'))}
-
-
 def set_option(name, value):
-    """Process-wide tuning / test switch of libvsx (see include/vsx.h: "gemm_pp", "pp_sched", "tile_tune").  The values are
-    mirrored here for the host-side choices that depend on them (`_subpixel_eligible`, `_winograd_eligible`)."""
+    """Process-wide tuning / test switch of libvsx (the table in csrc/options.cpp).  The library holds the only copy: the
+    host-side choices that depend on an option (`_conv_form`) ask the library, which reads it there."""
     check(_lib.load().vsx_set_option(name.encode(), int(value)), 'vsx_set_option')
-    _options[name] = int(value)
+
+
+def get_option(name):
+    """The current value of a libvsx option (its environment variable's, or the default, until `set_option`)."""
+    value = ctypes.c_int64()
+    check(_lib.load().vsx_get_option(name.encode(), ctypes.byref(value)), 'vsx_get_option')
+    return value.value
 
 
 _prof_state = {'on': 0, 'max': 0, 'stride': 1, 'paused': False}
@@ -1232,7 +1199,7 @@ _ACTIVATIONS = {
     'unpack_latents': ((0,), ()), 'cfg_ddim_step': ((0, 1, 2), ()), 'masked_blend': ((0, 1), ()),
     'adapter_scatter': ((2,), ()),
 }
-_PLAIN = ('gemm', 'set_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'softmax_rows', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
+_PLAIN = ('gemm', 'set_option', 'get_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'softmax_rows', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
           'hash_mlp', 'atlas_edit')
