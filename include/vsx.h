@@ -535,6 +535,45 @@ int vsx_atlas_edit_f32(const float* uv_fg, const float* uv_bg, const float* alph
                        float bg_pixel_size, const float* base_bg, float* mask_bg, int64_t mask_bg_h, int64_t mask_bg_w,
                        float* edit, float* fg, float* bg, uint8_t* relevant, vsx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K16 (ABI 15, additive): weight and bias gradients of the K13 coordinate MLP, for fitting the mapping networks of an atlas
+ * (pretrain_mapping, the inverse-mapping fit).  fp32 throughout on v_mfma_f32_32x32x2_f32; no gradient with respect to x;
+ * no atomics: two calls on the same inputs give the same bits (csrc/atlas_bwd.hip).  The options, their
+ * limits and the words of a refusal are K13's; E = the encoded width (input_dim, or 2 * input_dim * pe_dim), L = mlp_layers.
+ * vsx_coord_mlp_train_workspace: the float counts of `saved`, of the backward's `scratch` and of `grad` for N rows (any of
+ *   the three pointers may be NULL).  saved = N * ((L - 1) * hidden_dim + E + output_dim);
+ *   scratch = ceil(N / R) * grad + 2 * N * hidden_dim + N * output_dim with R = vsx_coord_mlp_wgrad_rows() (512).
+ * vsx_coord_mlp_fwd_train_f32: vsx_coord_mlp_f32 (the same kernel source, `out` bit-identical) that also fills `saved`
+ *   (16-byte aligned), for the rows < N only:
+ *     [L - 1][N][hidden_dim]  the activation of hidden layer l after its ReLU, l = 0 .. L - 2
+ *     [N][E]                  the encoded input (the coordinates themselves with pe_type none), unpadded
+ *     [N][output_dim]         out
+ * vsx_coord_mlp_bwd_f32: grad_out [N, output_dim], `saved` as written above, `packed` as K13 -> grad, one flat buffer: per
+ *   layer, in the order hidden.0 .. hidden.L-1, the weight gradient [out, in] row-major in the nn.Linear layout (UNPADDED;
+ *   in = hidden columns, then the E encoded columns of layer 0 and of the skip layers), then the bias gradient [out].
+ *     dZ_L = grad_out, times (1 - out^2) with use_tanh;  dW_l = dZ_l^T In_l,  db_l = the column sums of dZ_l, In_l =
+ *     cat(H_{l-1}, enc);  dZ_{l-1} = (dZ_l W_l[:, :hidden_dim]) where the STORED H_{l-1} > 0, else 0.  The encoded columns of a
+ *     skip layer receive weight gradients and pass none on (the reference concatenates a detached copy).
+ *   Summation over rows: chunks of R rows; inside a chunk four interleaved partial sums of R / 4 rows each, added pairwise;
+ *   the chunks' results are added in index order by a last launch.  2 L + 1 launches whatever N is.  Rows >= N are never read.
+ *   N == 0: grad is set to zero, nothing is launched.  scratch is overwritten.
+ *   Refused, nothing written: an unsupported option (VSX_E_UNSUPPORTED); saved, scratch or grad shorter than the workspace
+ *   query says (VSX_E_WORKSPACE); a null pointer, a packed buffer of another size (VSX_E_BADSHAPE).
+ * ------------------------------------------------------------------------------------------ */
+int64_t vsx_coord_mlp_wgrad_rows(void);
+int vsx_coord_mlp_train_workspace(int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers,
+                                  int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask, int64_t* saved_floats,
+                                  int64_t* scratch_floats, int64_t* grad_floats);
+int vsx_coord_mlp_fwd_train_f32(const float* x, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
+                                int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask,
+                                int64_t use_tanh, const float* packed, int64_t packed_floats, float* out, float* saved,
+                                int64_t saved_floats, vsx_stream_t stream);
+int vsx_coord_mlp_bwd_f32(const float* grad_out, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
+                          int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask,
+                          int64_t use_tanh, const float* packed, int64_t packed_floats, const float* saved,
+                          int64_t saved_floats, float* scratch, int64_t scratch_floats, float* grad, int64_t grad_floats,
+                          vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,12 @@ PROTOTYPES = {
     'vsx_atlas_edit_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int64]
                            + ([c_void_p] + [c_int64] * 3 + [c_float] * 3 + [c_void_p, c_void_p, c_int64, c_int64]) * 2
                            + [c_void_p] * 5),
+    # weight and bias gradients of the coordinate MLP (csrc/atlas_bwd.hip, K16; the training forward lives in atlas.hip)
+    'vsx_coord_mlp_wgrad_rows': (c_int64, []),
+    'vsx_coord_mlp_train_workspace': (c_int, [c_int64] * 9 + [c_void_p] * 3),
+    'vsx_coord_mlp_fwd_train_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                                                          c_void_p]),
+    'vsx_coord_mlp_bwd_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64] * 4 + [c_void_p]),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

@@ -13,7 +13,10 @@ all five networks of a checkpoint, the texture network `F_Atlas` behind its hash
 give the reconstruction, the alpha matte, the atlas textures and the PSNR.  The hash grid is restated from the published
 tiny-cuda-nn algorithm and has NOT been compared with tinycudann.  Editing (the third part) restates the
 texture-reading half of evaluate_model (:344-419): the video re-rendered from EDITED texture images through `ops.atlas_edit`
-(csrc/atlas_edit.hip).  Training an atlas (train_atlas.py, the losses) is out of scope.
+(csrc/atlas_edit.hip).  Fitting (videoswap_amd/atlas_fit.py): a `CoordMLP` switched on with
+`differentiable_(True)` has weight and bias gradients (csrc/atlas_bwd.hip), which is what mapping pre-training
+(`pretrain_mapping`) and the inverse-mapping fit (`fit_inverse_mapping`) need; both are in scope.  Full atlas training
+(train_atlas.py: the gradients of the hash grid and of F_Atlas's input, the losses) is not.
 """
 import json
 import math
@@ -106,8 +109,18 @@ class CoordMLP(_LayerStack):
             raise NotImplementedError(f"CoordMLP: mlp_type {mlp_type!r} is not implemented, only 'origin' (nn.Linear layers)")
         super().__init__(input_dim, output_dim, hidden_dim, pe_type, pe_dim, mlp_type, skip_layers, mlp_layers, use_tanh)
         self._build_hidden(2 * self.input_dim * self.pe_dim if pe_type == 'encoding' else self.input_dim)
+        self._differentiable = False
+
+    def differentiable_(self, flag=True):
+        """Switch the gradient path on (off by default) -> self.  On, and while grad mode is on and a parameter requires
+        grad, `forward` records weight and bias gradients (atlas_fit.CoordMLPFunction); there is none for the input."""
+        self._differentiable = bool(flag)
+        return self
 
     def _launch(self, x):
+        if self._differentiable and torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
+            from .atlas_fit import differentiable_forward
+            return differentiable_forward(self, x)
         return ops.coord_mlp(x, self.packed(), self.input_dim, self.output_dim, self.hidden_dim, self.mlp_layers,
                              pe_type=self.pe_type, pe_dim=self.pe_dim, mlp_type=self.mlp_type, skip_layers=self.skip_layers,
                              use_tanh=self.use_tanh)
@@ -541,3 +554,6 @@ def checkerboard_videos(models, res_x, res_y, number_of_frames, area_fg, area_bg
     cfg = torch.where((rel & 1) != 0, 0.5 * (1.0 - out['alpha']).unsqueeze(-1) + out['edited_fg'], half)
     cbg = torch.where((rel & 2) != 0, out['edited_bg'], half)
     return dict(checkerboard_fg=cfg, checkerboard_bg=cbg, texture_fg=texs[0], texture_bg=texs[1], launches=out['launches'] + 2)
+
+
+from .atlas_fit import fit_inverse_mapping, load_mask_frames, pretrain_mapping  # noqa: E402,F401  (the fitting half)

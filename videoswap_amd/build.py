@@ -31,7 +31,7 @@ VARIANTS = {}
 # variant name -> additional sources (relative to csrc/)
 VARIANT_EXTRA = {}
 SOURCES = ['api.cpp', 'comm.cpp', 'options.cpp', 'prof.cpp', 'gemm.hip', 'gemm_pp.hip', 'norm.hip', 'attention.hip', 'attention_bwd.hip', 'elementwise.hip',
-           'train.hip', 'dift.hip', 'atlas.hip', 'atlas_edit.hip', 'winograd.hip']
+           'train.hip', 'dift.hip', 'atlas.hip', 'atlas_bwd.hip', 'atlas_edit.hip', 'winograd.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-x', 'hip',
          '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-Wall', '-Wno-unused-function', '-Wno-division-by-zero',

@@ -24,19 +24,15 @@
 // with tinycudann.
 #include <math.h>
 
-#include "common.h"
+#include "coord_mlp.h"
 
 namespace {
-
-constexpr int CM_BM = 64;            // rows per workgroup
-constexpr int CM_THREADS = 256;
-constexpr int CM_MAX_LAYERS = 8;
-constexpr int CM_MAX_ENC = 64;       // encoded input columns (2 * input_dim * pe_dim), padded to a multiple of 8
 
 struct CoordMlpParams {
     const float* x;
     const float* w;                  // packed weights and biases (vsx.h)
     float* out;
+    float* saved;                    // the training instantiation's stores (vsx.h K16); unused otherwise
     long N;
     int in_dim, out_dim, hidden, layers;
     int pe_dim;                      // 0: pe_type none
@@ -165,8 +161,11 @@ __device__ __forceinline__ void cm_layer(f16v (&acc)[2][2], const CoordMlpParams
     if (kbe) cm_accumulate<NF, NR, S>(acc, wl, kbh + kbe, kbh, kbe, enc, ft, rt0, lane);
 }
 
-template <class Grid>
+// Train: the same arithmetic, and every row < N also stores what the backward reads (vsx.h K16): the encoded input, every
+// hidden layer's activation after its ReLU, and the output.
+template <class Grid, bool Train = false>
 __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpParams p, const Grid g) {
+    static_assert(!(Train && Grid::kHash), "the hash grid has no backward");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f4v* act = reinterpret_cast<f4v*>(smem);                       // [hidden / 4][CM_BM]
     f4v* enc = act + (p.hidden / 4) * CM_BM;                       // [encp / 4][CM_BM]
@@ -206,6 +205,9 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
                 }
             }
             reinterpret_cast<float*>(enc)[((e >> 2) * CM_BM + r) * 4 + (e & 3)] = v;
+            if constexpr (Train) {
+                if (e < p.enc && row0 + r < p.N) p.saved[(long)(p.layers - 1) * p.N * p.hidden + (row0 + r) * p.enc + e] = v;
+            }
         }
     }
     __syncthreads();
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
                         float v = acc[0][0][s] + bias[s];
                         if (p.use_tanh) v = tanhf(v);
                         p.out[row * p.out_dim + s] = v;
+                        if constexpr (Train) p.saved[((long)(p.layers - 1) * p.hidden + p.enc) * p.N + row * p.out_dim + s] = v;
                     }
                 }
             }
@@ -264,6 +267,10 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
 #pragma unroll
                         for (int s = 0; s < 4; ++s) v[s] = fmaxf(acc[f][r][4 * g + s] + b[s], 0.f);   // ReLU before the next layer
                         act[(fb >> 2) * CM_BM + (rt0 + r) * 32 + (lane & 31)] = v;
+                        if constexpr (Train) {
+                            const long row = row0 + (rt0 + r) * 32 + (lane & 31);
+                            if (row < p.N) *reinterpret_cast<f4v*>(p.saved + ((long)l * p.N + row) * p.hidden + fb) = v;
+                        }
                     }
                 }
             }
@@ -291,33 +298,14 @@ __global__ __launch_bounds__(CM_THREADS) void hash_grid_kernel(const float* __re
     }
 }
 
-inline long cm_round_up(long x, long m) { return (x + m - 1) / m * m; }
-
-// floats of the packed weight buffer (vsx.h) of a network with `enc` encoded columns, arguments already validated
-long cm_packed_floats(int64_t enc, int64_t hidden_dim, int64_t mlp_layers, int64_t skip_mask) {
-    const long encp = cm_round_up(enc, 8);
-    long total = 0;
-    for (int l = 0; l < mlp_layers; ++l) {
-        const long fp = l == mlp_layers - 1 ? 32 : hidden_dim;
-        const long kp = (l > 0 ? hidden_dim : 0) + ((l == 0 || ((skip_mask >> l) & 1)) ? encp : 0);
-        total += fp * kp + fp;
-    }
-    return total;
-}
-
 // The layer stack's half of an entry point: validates it (every message under `what`; the unsupported options before
 // N == 0, which the CALLER answers with VSX_OK after this returns VSX_OK) and fills the kernel arguments for `enc` encoded
 // columns; pe_dim 0: the columns are not the sin/cos encoding.
 int cm_prepare(const char* what, CoordMlpParams& p, const float* x, int64_t N, int64_t input_dim, int64_t output_dim,
                int64_t hidden_dim, int64_t mlp_layers, int64_t pe_dim, int64_t enc, int64_t skip_mask, int64_t use_tanh,
                const float* packed, int64_t packed_floats, float* out) {
-    VSX_REQUIRE(output_dim >= 1 && output_dim <= 3, VSX_E_UNSUPPORTED, "%s: output_dim %lld (1 to 3)", what, (long long)output_dim);
-    VSX_REQUIRE(hidden_dim >= 32 && hidden_dim <= 256 && hidden_dim % 32 == 0, VSX_E_UNSUPPORTED,
-                "%s: hidden_dim %lld (a multiple of 32 up to 256)", what, (long long)hidden_dim);
-    VSX_REQUIRE(mlp_layers >= 2 && mlp_layers <= CM_MAX_LAYERS, VSX_E_UNSUPPORTED, "%s: mlp_layers %lld (2 to 8)", what,
-                (long long)mlp_layers);
-    VSX_REQUIRE(skip_mask >= 0 && (skip_mask & 1) == 0 && (skip_mask >> mlp_layers) == 0, VSX_E_UNSUPPORTED,
-                "%s: skip_layers must lie in 1 .. mlp_layers - 1 (mask 0x%llx)", what, (long long)skip_mask);
+    const int src = cm_check_stack(what, output_dim, hidden_dim, mlp_layers, skip_mask);
+    if (src != VSX_OK) return src;
     VSX_REQUIRE(N >= 0 && N < (1ll << 31) * CM_BM, VSX_E_BADSHAPE, "%s: N = %lld", what, (long long)N);
     if (N == 0) return VSX_OK;
     VSX_REQUIRE(x && packed && out, VSX_E_BADSHAPE, "%s: null argument", what);
@@ -326,7 +314,7 @@ int cm_prepare(const char* what, CoordMlpParams& p, const float* x, int64_t N, i
     VSX_REQUIRE(packed_floats == need, VSX_E_BADSHAPE, "%s: packed weights hold %lld floats, this network needs %lld", what,
                 (long long)packed_floats, (long long)need);
 
-    p.x = x, p.w = packed, p.out = out, p.N = N;
+    p.x = x, p.w = packed, p.out = out, p.saved = nullptr, p.N = N;
     p.in_dim = (int)input_dim, p.out_dim = (int)output_dim, p.hidden = (int)hidden_dim, p.layers = (int)mlp_layers;
     p.pe_dim = (int)pe_dim;
     p.enc = (int)enc, p.encp = (int)cm_round_up(enc, 8);
@@ -336,24 +324,24 @@ int cm_prepare(const char* what, CoordMlpParams& p, const float* x, int64_t N, i
         p.w_off[l] = p.b_off[l] = 0;
         if (l >= mlp_layers) continue;
         const long fp = l == mlp_layers - 1 ? 32 : hidden_dim;
-        const long kp = (l > 0 ? hidden_dim : 0) + ((l == 0 || ((skip_mask >> l) & 1)) ? p.encp : 0);
+        const long kp = (l > 0 ? hidden_dim : 0) + (cm_has_enc(l, skip_mask) ? p.encp : 0);
         p.w_off[l] = (int)off, p.b_off[l] = (int)(off + fp * kp);
         off += fp * kp + fp;
     }
     return VSX_OK;
 }
 
-template <class Grid>
+template <class Grid, bool Train = false>
 int cm_launch(const char* what, const CoordMlpParams& p, const Grid& g, vsx_stream_t stream) {
     const size_t smem = (size_t)(p.hidden + p.encp) * CM_BM * sizeof(float);     // <= 80 KiB: two workgroups per CU
     static size_t smem_attr = 64 * 1024;
     if (smem > smem_attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&coord_mlp_kernel<Grid>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&coord_mlp_kernel<Grid, Train>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return vsx_fail(VSX_E_LAUNCH, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
         smem_attr = 160 * 1024;
     }
-    hipLaunchKernelGGL(coord_mlp_kernel<Grid>, dim3((unsigned)((p.N + CM_BM - 1) / CM_BM)), dim3(CM_THREADS), smem,
+    hipLaunchKernelGGL((coord_mlp_kernel<Grid, Train>), dim3((unsigned)((p.N + CM_BM - 1) / CM_BM)), dim3(CM_THREADS), smem,
                        (hipStream_t)stream, p, g);
     return vsx_check_launch(what);
 }
@@ -414,19 +402,34 @@ extern "C" int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, i
                                  int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type, int64_t skip_mask,
                                  int64_t use_tanh, const float* packed, int64_t packed_floats, float* out,
                                  vsx_stream_t stream) {
-    VSX_REQUIRE(mlp_type == 0, VSX_E_UNSUPPORTED, "coord_mlp: mlp_type 'tcnn' (%lld) is not implemented, only 'origin'",
-                (long long)mlp_type);
-    VSX_REQUIRE(pe_type == 0 || pe_type == 1, VSX_E_UNSUPPORTED,
-                "coord_mlp: pe_type 'hash_encoding' (%lld) is not implemented, only 'none' and 'encoding'", (long long)pe_type);
-    VSX_REQUIRE(input_dim == 2 || input_dim == 3, VSX_E_UNSUPPORTED, "coord_mlp: input_dim %lld (2 or 3)", (long long)input_dim);
-    const int64_t enc = pe_type == 1 ? 2 * input_dim * pe_dim : input_dim;
-    VSX_REQUIRE(pe_type == 0 || (pe_dim >= 1 && enc <= CM_MAX_ENC), VSX_E_UNSUPPORTED,
-                "coord_mlp: pe_dim %lld (2 * input_dim * pe_dim must be 1 to %d)", (long long)pe_dim, CM_MAX_ENC);
+    int64_t enc = 0;
+    const int orc = cm_check_options("coord_mlp", mlp_type, pe_type, input_dim, pe_dim, &enc);
+    if (orc != VSX_OK) return orc;
     CoordMlpParams p;
     const int rc = cm_prepare("coord_mlp", p, x, N, input_dim, output_dim, hidden_dim, mlp_layers, pe_type == 1 ? pe_dim : 0, enc,
                               skip_mask, use_tanh, packed, packed_floats, out);
     if (rc != VSX_OK || N == 0) return rc;
     return cm_launch("vsx_coord_mlp_f32", p, NoGrid{}, stream);
+}
+
+// K16, the forward half: vsx_coord_mlp_f32 with the stores of the training instantiation
+extern "C" int vsx_coord_mlp_fwd_train_f32(const float* x, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
+                                           int64_t mlp_layers, int64_t pe_type, int64_t pe_dim, int64_t mlp_type,
+                                           int64_t skip_mask, int64_t use_tanh, const float* packed, int64_t packed_floats,
+                                           float* out, float* saved, int64_t saved_floats, vsx_stream_t stream) {
+    int64_t enc = 0;
+    const int orc = cm_check_options("coord_mlp_fwd_train", mlp_type, pe_type, input_dim, pe_dim, &enc);
+    if (orc != VSX_OK) return orc;
+    CoordMlpParams p;
+    const int rc = cm_prepare("coord_mlp_fwd_train", p, x, N, input_dim, output_dim, hidden_dim, mlp_layers,
+                              pe_type == 1 ? pe_dim : 0, enc, skip_mask, use_tanh, packed, packed_floats, out);
+    if (rc != VSX_OK || N == 0) return rc;
+    VSX_REQUIRE(saved && vsx_aligned16(saved), VSX_E_BADSHAPE, "coord_mlp_fwd_train: saved must be a 16-byte aligned buffer");
+    const int64_t need = cm_saved_floats(N, enc, output_dim, hidden_dim, mlp_layers);
+    VSX_REQUIRE(saved_floats >= need, VSX_E_WORKSPACE, "coord_mlp_fwd_train: saved holds %lld floats, N = %lld needs %lld",
+                (long long)saved_floats, (long long)N, (long long)need);
+    p.saved = saved;
+    return cm_launch<NoGrid, true>("vsx_coord_mlp_fwd_train_f32", p, NoGrid{}, stream);
 }
 
 extern "C" int64_t vsx_hash_grid_geometry(int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,

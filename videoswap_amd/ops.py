@@ -897,6 +897,81 @@ def coord_mlp(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type=
     return out
 
 
+COORD_MLP_WGRAD_ROWS = 512     # vsx_coord_mlp_wgrad_rows(): rows per chunk of the weight-gradient reduction (csrc/atlas_bwd.hip)
+
+
+def _coord_net(what, input_dim, output_dim, hidden_dim, mlp_layers, pe_type, pe_dim, mlp_type, skip_layers):
+    """the nine integers by which the K13 / K16 entry points know a network"""
+    if pe_type not in _COORD_PE:
+        raise NotImplementedError(f'{what}: pe_type {pe_type!r} (IMLP_Hash knows none / encoding / hash_encoding)')
+    if mlp_type not in _COORD_MLP:
+        raise NotImplementedError(f'{what}: mlp_type {mlp_type!r} (IMLP_Hash knows origin / tcnn)')
+    return (int(input_dim), int(output_dim), int(hidden_dim), int(mlp_layers), _COORD_PE[pe_type], int(pe_dim),
+            _COORD_MLP[mlp_type], _skip_mask(skip_layers, what))
+
+
+def coord_mlp_train_workspace(N, input_dim, output_dim, hidden_dim, mlp_layers, pe_type='none', pe_dim=0, mlp_type='origin',
+                              skip_layers=()):
+    """-> (saved, scratch, grad): the float counts of the three buffers of a training step over N rows (vsx.h K16)"""
+    net = _coord_net('coord_mlp_train_workspace', input_dim, output_dim, hidden_dim, mlp_layers, pe_type, pe_dim, mlp_type,
+                     skip_layers)
+    counts = [ctypes.c_int64(0) for _ in range(3)]
+    rc = _lib.load().vsx_coord_mlp_train_workspace(int(N), *net, *(ctypes.addressof(c) for c in counts))
+    _check_supported(rc, 'vsx_coord_mlp_train_workspace')
+    return tuple(int(c.value) for c in counts)
+
+
+def coord_mlp_train_forward(x, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type='none', pe_dim=0,
+                            mlp_type='origin', skip_layers=(), use_tanh=True, saved=None):
+    """`coord_mlp` (the same kernel source, the same bits) that also stores what `coord_mlp_backward` reads -> (out, saved):
+    saved fp32, flat (vsx.h K16: the hidden activations after their ReLU, the encoded input, out).  `saved`: a buffer to
+    fill instead of a new one; one shorter than `coord_mlp_train_workspace` says is refused (VsxError)."""
+    net = _coord_net('coord_mlp_train_forward', input_dim, output_dim, hidden_dim, mlp_layers, pe_type, pe_dim, mlp_type, skip_layers)
+    _chk(x, 'x', torch.float32)
+    _chk(packed, 'packed', torch.float32)
+    _chk(saved, 'saved', torch.float32)
+    if x.dim() != 2 or x.shape[1] != input_dim:
+        raise _lib.VsxError(f'coord_mlp_train_forward: x must be [N, {input_dim}], got {tuple(x.shape)}')
+    lib = _lib.load()
+    if saved is None:
+        floats = ctypes.c_int64(0)
+        _check_supported(lib.vsx_coord_mlp_train_workspace(x.shape[0], *net, ctypes.addressof(floats), None, None),
+                         'vsx_coord_mlp_train_workspace')
+        saved = torch.empty(floats.value, dtype=torch.float32, device=x.device)
+    out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
+    rc = lib.vsx_coord_mlp_fwd_train_f32(_p(x), x.shape[0], *net, int(bool(use_tanh)), _p(packed), packed.numel(), _p(out),
+                                         _p(saved), saved.numel(), _stream())
+    _check_supported(rc, 'vsx_coord_mlp_fwd_train_f32')
+    return out, saved
+
+
+def coord_mlp_backward(grad_out, saved, packed, input_dim, output_dim, hidden_dim, mlp_layers, pe_type='none', pe_dim=0,
+                       mlp_type='origin', skip_layers=(), use_tanh=True, grad=None):
+    """Weight and bias gradients of the network `coord_mlp_train_forward` ran: grad_out fp32 [N, output_dim], `saved` and
+    `packed` of that call -> one flat fp32 buffer: per layer the weight gradient [out, in] (nn.Linear layout, unpadded),
+    then the bias gradient.  No gradient with respect to x.  Deterministic: no atomics, a fixed summation order.  `grad`:
+    a buffer to fill instead of a new one; a short `saved` or `grad` is refused (VsxError)."""
+    net = _coord_net('coord_mlp_backward', input_dim, output_dim, hidden_dim, mlp_layers, pe_type, pe_dim, mlp_type, skip_layers)
+    _chk(grad_out, 'grad_out', torch.float32)
+    _chk(saved, 'saved', torch.float32)
+    _chk(packed, 'packed', torch.float32)
+    _chk(grad, 'grad', torch.float32)
+    if grad_out.dim() != 2 or grad_out.shape[1] != output_dim:
+        raise _lib.VsxError(f'coord_mlp_backward: grad_out must be [N, {output_dim}], got {tuple(grad_out.shape)}')
+    lib = _lib.load()
+    N = grad_out.shape[0]
+    counts = [ctypes.c_int64(0) for _ in range(2)]
+    _check_supported(lib.vsx_coord_mlp_train_workspace(N, *net, None, *(ctypes.addressof(c) for c in counts)),
+                     'vsx_coord_mlp_train_workspace')
+    scratch = torch.empty(counts[0].value, dtype=torch.float32, device=grad_out.device)
+    if grad is None:
+        grad = torch.empty(counts[1].value, dtype=torch.float32, device=grad_out.device)
+    rc = lib.vsx_coord_mlp_bwd_f32(_p(grad_out), N, *net, int(bool(use_tanh)), _p(packed), packed.numel(), _p(saved), saved.numel(),
+                                   _p(scratch), scratch.numel(), _p(grad), grad.numel(), _stream())
+    _check_supported(rc, 'vsx_coord_mlp_bwd_f32')
+    return grad
+
+
 def _hash_grid_args(x, table, grid, what):
     """(input_dim, table_floats, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale) of a call"""
     _chk(x, 'x', torch.float32)
@@ -1202,7 +1277,7 @@ _ACTIVATIONS = {
 _PLAIN = ('gemm', 'set_option', 'get_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'softmax_rows', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
-          'hash_mlp', 'atlas_edit')
+          'hash_mlp', 'atlas_edit', 'coord_mlp_train_workspace', 'coord_mlp_train_forward', 'coord_mlp_backward')
 
 
 def _publish(name):
