@@ -218,7 +218,8 @@ int vsx_layernorm(const void* x, int64_t M, int64_t C, const void* gamma, const 
  *   O  [nb, nq, heads*d]  row stride ldo
  * image b uses K/V image b / kv_div (kv_div = frames for cross-attention where the text
  * embedding is shared by all frames: the reference repeats it, attention.py:100-103).
- * d in {8,16,32,40,64,80,128,160}.
+ * d in {8,16,32,40,64,80,128,160}.  scale > 0 and finite (the kernel takes the row max before scaling);
+ * anything else is VSX_E_BADSHAPE and nothing is launched.
  * ------------------------------------------------------------------------------------------ */
 int vsx_attention_f16(const void* Q, const void* K, const void* VT, void* O, int64_t nb,
                       int64_t heads, int64_t nq, int64_t nk, int64_t d, int64_t ldq, int64_t ldk,
@@ -236,7 +237,8 @@ int vsx_attention_f16(const void* Q, const void* K, const void* VT, void* O, int
  *       QT, dOT [nb, heads*d, ldtq], KT [nb / kv_div, heads*d, ldtk]: per-image transposes, rows zero-padded to a multiple
  *       of 8 (QT / dOT only for dK / dV); lse, delta [nb, heads, lds], lds a multiple of 64, zero beyond nq.
  *       kv_div > 1 (text K / V shared by the frames of a clip): dQ only.  d in {40, 64, 80}
- *       (vsx_attention_bwd_supported); other head dims keep the materialised path of videoswap_amd/autograd.py. */
+ *       (vsx_attention_bwd_supported); other head dims keep the materialised path of videoswap_amd/autograd.py.
+ *   Both require scale > 0 and finite, as vsx_attention_f16 (VSX_E_BADSHAPE otherwise, nothing launched). */
 int vsx_attention_lse_f16(const void* Q, const void* K, const void* VT, void* O, float* lse, int64_t lse_ld, int64_t nb,
                           int64_t heads, int64_t nq, int64_t nk, int64_t d, int64_t ldq, int64_t ldk, int64_t ldvt,
                           int64_t ldo, int64_t q_bs, int64_t k_bs, int64_t vt_bs, int64_t o_bs, int64_t kv_div,
@@ -258,7 +260,8 @@ int vsx_softmax_rows_causal(void* S, int64_t nrows, int64_t ncols, int64_t ld, i
 
 /* K8: temporal self-attention across frames at every spatial site (motion_module.py:287-338),
  * computed directly on the [B, F, HW, heads*d] layout (no transposes).  q/k/v/o share row
- * stride ld.  In frame-sharded mode q holds the local fq frames and k/v the gathered fk frames. */
+ * stride ld.  In frame-sharded mode q holds the local fq frames and k/v the gathered fk frames.
+ * Any finite scale: all three kernels scale the scores before they take the row max. */
 int vsx_temporal_attention_f16(const void* Q, const void* K, const void* V, void* O, int64_t B,
                                int64_t fq, int64_t fk, int64_t hw, int64_t heads, int64_t d,
                                int64_t ldq, int64_t ldkv, int64_t ldo, float scale,

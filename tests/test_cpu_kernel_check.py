@@ -148,7 +148,9 @@ def test_attention_kernels_run_on_the_cpu(tmp_path):
     """csrc/attention.hip on the host: the flash kernel (d = 40 / 64 / 80 / 160, ragged query and key tiles, K / V shared by two
     query batches), the temporal kernel with (site, head) problems packed into 32x32 MFMA tiles (16 and 24 frames, 4 frames with 8
     heads per tile), its long-clip form (16 x 64, 8 x 40 frames) and the VALU fallback, against a double-precision
-    softmax(Q K^T) V (tools/cpu_check/check_attention.cpp; two textual rewrites of the source, attention_cpu.sed)."""
+    softmax(Q K^T) V (tools/cpu_check/check_attention.cpp; two textual rewrites of the source, attention_cpu.sed).  Also the
+    smallest edge shapes of tests/attention_case.py (flash 1 x 1, 33 x 9, 129 x 65; temporal 5 x 16 frames with 5 heads, 17 x 17,
+    1 x 33), where an index past a buffer shows on the host first, and the refusal of a scale that is not positive."""
     cxx = CXX if os.path.isfile(CXX) else shutil.which('clang++')
     src = os.path.join(ROOT, 'tools', 'cpu_check')
     gen = tmp_path / 'gen'
@@ -172,8 +174,9 @@ def test_attention_kernels_run_on_the_cpu(tmp_path):
 
 def test_attention_backward_kernels_run_on_the_cpu(tmp_path):
     """csrc/attention_bwd.hip on the host: the dQ kernel and the dK / dV kernel of the flash-attention backward (d = 40 / 64 /
-    80, ragged query and key tiles, text K / V shared by two images) and the delta kernel, against double-precision
-    gradients of softmax(scale Q K^T) V (tools/cpu_check/check_attention_bwd.cpp)."""
+    80, ragged query and key tiles, text K / V shared by two images; 1 x 1, 65 x 129 and 129 x 65) and the delta kernel, against
+    double-precision gradients of softmax(scale Q K^T) V, and the refusal of a scale that is not positive
+    (tools/cpu_check/check_attention_bwd.cpp)."""
     cxx = CXX if os.path.isfile(CXX) else shutil.which('clang++')
     src = os.path.join(ROOT, 'tools', 'cpu_check')
     exe = str(tmp_path / 'check_attention_bwd')

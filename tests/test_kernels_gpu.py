@@ -6,7 +6,9 @@ All calls go through the C ABI (videoswap_amd.ops -> ctypes -> libvsx.so).
 
 The kernels of the training step (csrc/train.hip: GEGLU, SiLU, GroupNorm, LayerNorm and softmax backward, the 2x2 sum pool,
 adapter_gather) and quick_gelu, silu and the two row softmaxes have their parity tests in tests/test_train_kernels_gpu.py:
-each on its own against fp64, with bounds taken from the fp32 ideal on the same inputs.
+each on its own against fp64, with bounds taken from the fp32 ideal on the same inputs.  The attention kernels (flash forward
+and backward, temporal, the materialised path) are pinned the same way at tile-edge shapes in
+tests/test_attention_kernels_gpu.py; the attention tests below keep the model's own shapes.
 """
 import math
 
@@ -750,7 +752,10 @@ def test_attention_backward_flash(nb, heads, nq, nk, d, kv_div):
     qh = q.float().view(nb, nq, heads, d).transpose(1, 2)
     kh = k.float().view(nb // kv_div, nk, heads, d).transpose(1, 2).repeat_interleave(kv_div, 0)
     want_lse = torch.logsumexp(qh @ kh.transpose(-1, -2) * scale, -1) * 1.4426950408889634
-    assert (lse[..., :nq] - want_lse).abs().max() < 2e-2 and float(lse[..., nq:].abs().sum()) == 0.0
+    # the derived bound of tests/attention_case.py: a denominator of terms each within 2^-11 relative (log2 domain: x 1.4427),
+    # 16 fp32 ulps for s c - m and the log2; the fp32 reference's own error is inside the second term
+    lse_bound = 1.4427 * 2.0 ** -11 + 2.0 ** -20 * want_lse.abs().clamp_min(1.0)
+    assert bool(((lse[..., :nq] - want_lse).abs() <= lse_bound).all()) and float(lse[..., nq:].abs().sum()) == 0.0
     self_attn = kv_div == 1
     dq, dk, dv = ops().attention_bwd(q, k, v, out, g, lse, heads, scale, kv_div=kv_div, need_kv=self_attn)
     assert rel_err(dq, qr.grad, l2_tol=4e-3, row_tol=2e-2) < 8e-3

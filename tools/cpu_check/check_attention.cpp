@@ -162,6 +162,35 @@ int main(int argc, char** argv) {
     if (only < 0 || only == 8) run_temporal("temporal long clip d = 40: 16 local query frames x 64 key frames", 1, 16, 64, 2, 8, 40);
     if (only < 0 || only == 9) run_temporal("temporal long clip d = 80: 8 x 40", 1, 8, 40, 1, 8, 80);
     if (only < 0 || only == 10) run_temporal("temporal fallback d = 24 (VALU kernel), 6 x 9 frames", 1, 6, 9, 2, 3, 24);
+    // the smallest edge shapes of tests/attention_case.py: less than one query block / key tile, one past a tile
+    g_attn_o16 = 0;
+    if (only < 0 || only == 17) run_flash("flash d = 40, 1 x 1", 2, 1, 2, 1, 1, 40);
+    if (only < 0 || only == 18) run_flash("flash d = 40, 33 x 9", 2, 1, 2, 33, 9, 40);
+    if (only < 0 || only == 19) run_flash("flash d = 40, 129 x 65", 2, 1, 2, 129, 65, 40);
+    if (only < 0 || only == 20) run_flash("flash d = 64, 1 x 1", 2, 1, 2, 1, 1, 64);
+    if (only < 0 || only == 21) run_flash("flash d = 64, 33 x 9", 2, 1, 2, 33, 9, 64);
+    if (only < 0 || only == 22) run_flash("flash d = 64, 129 x 65", 2, 1, 2, 129, 65, 64);
+    g_attn_o16 = 1;
+    if (only < 0 || only == 23) run_temporal("temporal d = 40, 5 x 16 frames (fq != fk), 5 heads", 1, 5, 16, 3, 5, 40);
+    if (only < 0 || only == 24) run_temporal("temporal d = 40, 17 x 17 frames (one head per tile, 15 idle columns)", 1, 17, 17, 3, 5, 40);
+    if (only < 0 || only == 25) run_temporal("temporal long clip d = 40: 1 x 33 frames", 1, 1, 33, 3, 5, 40);
+    if (only < 0 || only == 26) {      // the flash kernel takes the row max before scaling: a scale that is not positive is refused unlaunched
+        auto Q = randh(72 * 80), K = randh(72 * 80), VT = randh(80 * 72);
+        std::vector<float> lse(2 * 128, -7.f);
+        for (const float scale : {0.f, -0.158f, NAN, INFINITY}) {
+            std::vector<half_t> O(72 * 80, (half_t)-7.f);
+            const int rc = vsx_attention_f16(Q.data(), K.data(), VT.data(), O.data(), 1, 2, 72, 72, 40, 80, 80, 72, 80, 72 * 80, 72 * 80,
+                                             80 * 72, 72 * 80, 1, scale, nullptr);
+            const int rc2 = vsx_attention_lse_f16(Q.data(), K.data(), VT.data(), O.data(), lse.data(), 128, 1, 2, 72, 72, 40, 80, 80, 72, 80,
+                                                  72 * 80, 72 * 80, 80 * 72, 72 * 80, 1, scale, nullptr);
+            bool untouched = true;
+            for (const half_t o : O) untouched = untouched && (float)o == -7.f;
+            for (const float l : lse) untouched = untouched && l == -7.f;
+            const bool ok = rc != 0 && rc2 != 0 && untouched;
+            printf("flash refuses scale = %-42g rc %d / %d %s\n", (double)scale, rc, rc2, ok ? "ok" : "FAIL");
+            if (!ok) ++n_bad;
+        }
+    }
     printf(n_bad ? "%d check(s) FAILED\n" : "all checks passed\n", n_bad);
     return n_bad ? 1 : 0;
 }

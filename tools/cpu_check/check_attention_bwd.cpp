@@ -122,6 +122,29 @@ int main(int argc, char** argv) {
     if (only < 0 || only == 1) run("bwd d = 40, text K / V shared by 2 images, 150 x 77: dQ only", 2, 2, 2, 150, 77, 40, false);
     if (only < 0 || only == 2) run("bwd d = 80, 130 x 130", 1, 1, 1, 130, 130, 80, true);
     if (only < 0 || only == 3) run("bwd d = 64, 128 x 64 (exact tiles), 2 images", 2, 1, 1, 128, 64, 64, true);
+    // the smallest edge shapes of tests/attention_case.py: less than one tile of queries or keys, one past a tile
+    if (only < 0 || only == 4) run("bwd d = 40, 1 x 1", 2, 1, 2, 1, 1, 40, true);
+    if (only < 0 || only == 5) run("bwd d = 40, 65 x 129", 2, 1, 2, 65, 129, 40, true);
+    if (only < 0 || only == 6) run("bwd d = 40, 129 x 65", 2, 1, 2, 129, 65, 40, true);
+    if (only < 0 || only == 7) run("bwd d = 64, 1 x 1", 1, 1, 2, 1, 1, 64, true);
+    if (only < 0 || only == 8) run("bwd d = 80, 65 x 129", 1, 1, 2, 65, 129, 80, true);
+    if (only < 0 || only == 9) run("bwd d = 64, 129 x 65", 1, 1, 2, 129, 65, 64, true);
+    if (only < 0 || only == 10) {      // lse exists for a positive scale only: anything else is refused before the delta kernel
+        auto X = randh(8 * 40);
+        std::vector<float> lse(64, 0.f);
+        for (const float scale : {0.f, -0.158f, NAN, INFINITY}) {
+            std::vector<float> delta(64, -7.f);
+            std::vector<half_t> dQ(8 * 40, (half_t)-7.f), dK(8 * 40, (half_t)-7.f), dV(8 * 40, (half_t)-7.f);
+            const int rc = vsx_attention_bwd_f16(X.data(), X.data(), X.data(), X.data(), X.data(), X.data(), X.data(), X.data(), lse.data(),
+                                                 delta.data(), dQ.data(), dK.data(), dV.data(), 1, 1, 8, 8, 40, 8, 8, 64, 1, scale, nullptr);
+            bool untouched = true;
+            for (const float x : delta) untouched = untouched && x == -7.f;
+            for (size_t i = 0; i < dQ.size(); ++i) untouched = untouched && (float)dQ[i] == -7.f && (float)dK[i] == -7.f && (float)dV[i] == -7.f;
+            const bool ok = rc != 0 && untouched;
+            printf("bwd refuses scale = %-52g rc %d %s\n", (double)scale, rc, ok ? "ok" : "FAIL");
+            if (!ok) ++n_bad;
+        }
+    }
     printf(n_bad ? "%d check(s) FAILED\n" : "all checks passed\n", n_bad);
     return n_bad ? 1 : 0;
 }

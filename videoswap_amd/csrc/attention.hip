@@ -968,6 +968,9 @@ static int attention_fwd(const void* Q, const void* K, const void* VT, void* O, 
     VSX_REQUIRE(Q && K && VT && O, VSX_E_BADSHAPE, "attention: null tensor");
     if (nb == 0 || nq == 0) return VSX_OK;
     VSX_REQUIRE(nb > 0 && heads > 0 && nq > 0 && nk > 0 && kv_div > 0, VSX_E_BADSHAPE, "attention: bad sizes");
+    // the kernel takes a tile's row max BEFORE scaling (max commutes with a positive factor only), and with scale = 0 a masked
+    // score of the partial key tile would be -inf * 0; `!(scale > 0)` refuses a NaN too
+    VSX_REQUIRE(scale > 0.f && scale < INFINITY, VSX_E_BADSHAPE, "attention: scale must be positive and finite (got %g)", (double)scale);
     VSX_REQUIRE(nb <= 65535 && heads <= 65535, VSX_E_BADSHAPE, "attention: nb/heads exceed grid limits");
     VSX_REQUIRE(vsx_aligned16(Q) && vsx_aligned16(K) && vsx_aligned16(VT) && vsx_aligned16(O), VSX_E_BADSHAPE,
                 "attention: tensors must be 16-byte aligned");

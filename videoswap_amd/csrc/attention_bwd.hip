@@ -489,6 +489,8 @@ extern "C" int vsx_attention_bwd_f16(const void* Q, const void* K, const void* V
                 "attention_bwd: key / value gradients need Q^T, dO^T and unshared K / V");
     if (nb == 0 || nq == 0) return VSX_OK;
     VSX_REQUIRE(nb > 0 && heads > 0 && nq > 0 && nk > 0 && kv_div > 0 && nb % kv_div == 0, VSX_E_BADSHAPE, "attention_bwd: bad sizes");
+    // lse comes from vsx_attention_lse_f16, which exists for a positive scale only
+    VSX_REQUIRE(scale > 0.f && scale < INFINITY, VSX_E_BADSHAPE, "attention_bwd: scale must be positive and finite (got %g)", (double)scale);
     VSX_REQUIRE(vsx_attention_bwd_supported(d), VSX_E_UNSUPPORTED, "attention_bwd: head dim %ld not in {40, 64, 80}", (long)d);
     VSX_REQUIRE(ldtk % 8 == 0 && ldtk >= ((nk + 7) / 8) * 8 && (dK == nullptr || (ldtq % 8 == 0 && ldtq >= ((nq + 7) / 8) * 8)),
                 VSX_E_BADSHAPE, "attention_bwd: transposed rows must be padded to a multiple of 8");
