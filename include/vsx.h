@@ -577,6 +577,66 @@ int vsx_coord_mlp_bwd_f32(const float* grad_out, int64_t N, int64_t input_dim, i
                           int64_t saved_floats, float* scratch, int64_t scratch_floats, float* grad, int64_t grad_floats,
                           vsx_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * K17 (ABI 15, additive): the gradients of the K14 hash-grid network (the texture network F_Atlas): grid table, layer weights
+ * and biases, and the input x (csrc/atlas_bwd.hip, the training forward in csrc/atlas.hip).  fp32 throughout.
+ * The grid's options, their limits and the words of a refusal are K14's, the layer stack's are K13's; E = n_levels *
+ * n_features, L = mlp_layers.  The cell of a row on a level (pos_d, g_d, w_d, the four idx) is K14's, computed by the same
+ * device code as the forward.
+ * vsx_hash_mlp_train_workspace: the float counts of `saved`, `scratch` and `grad` for N rows (any pointer may be NULL).
+ *   saved = N * ((L - 1) * hidden_dim + E + output_dim);  grad = K16's (the layers only, K16's layout and order);
+ *   scratch = K16's (ceil(N / R) * grad + 2 * N * hidden_dim + N * output_dim) + N * E for dEnc.
+ * vsx_hash_mlp_fwd_train_f32: vsx_hash_mlp_f32 (the same kernel source, `out` bit-identical) that also fills `saved` (16-byte
+ *   aligned) in K16's layout, for the rows < N only: [L - 1][N][hidden_dim], [N][E] (the two features of every level, unpadded),
+ *   [N][output_dim].
+ * vsx_hash_mlp_bwd_f32: grad_out [N, output_dim], x [N, 2] and the table of the forward, `saved` as written above ->
+ *   1. grad: the K16 chain unchanged (the same kernels, K16's summation orders) on the saved activations.  No atomics: two
+ *      calls on the same inputs give the same bits.  The encoded columns of a skip layer receive weight gradients and pass
+ *      nothing on to the grid (the reference concatenates a detached copy); only layer 0 does.
+ *   2. dEnc [N, E] (in scratch) = dZ_0 W_0 over the E encoded columns of the packed layer 0, no mask: per element four
+ *      interleaved partial sums over the features f (f mod 8 in {0,4}, {1,5}, {2,6}, {3,7}, each in increasing f), added
+ *      pairwise (p_0 + p_1) + (p_2 + p_3).  A column >= E is neither read nor written.
+ *   3. the grid backward from dEnc, as vsx_hash_grid_bwd_f32 below.
+ *   grad_table [table_floats] (16-byte aligned) and grad_x [N, 2] may each be NULL: that gradient is not computed; with both
+ *   NULL steps 2 and 3 are not launched.  scratch is overwritten.  2 L + 1 launches, + 2 with a grid gradient, + the
+ *   clearing of grad_table, whatever N is.  N == 0: grad and grad_table are set to zero, nothing else is launched.
+ * vsx_hash_grid_bwd_f32: the grid backward alone: x [N, 2], grad_enc [N, E] -> grad_table, grad_x (each nullable).  Per row
+ *   and level l, with ga, gb = grad_enc[row][2 l], [2 l + 1]:
+ *     grad_table[offset + idx_c][f] += weight_c * grad_enc[row][2 l + f]   for the corners c = 0 .. 3, weight_c as in K14.
+ *       All table_floats of grad_table are first set to zero on the stream; the additions are fp32 atomic adds in global
+ *       memory, in no defined order: grad_table is NOT bit-reproducible from run to run (tiny-cuda-nn's is not either).
+ *       An entry that no corner of any row addresses stays exactly zero.
+ *     grad_x[row][d], d = 0, 1:  s_df = the sum over the corners c = 0 .. 3, in that order, of fmaf(sign * other,
+ *       table[offset + idx_c][f], sum), sign = +1 where bit d of c is set, else -1, other = the weight of c along the other
+ *       axis (w or 1 - w);  t_d = fmaf(gb, s_d1, ga * s_d0);  a wave owns the levels 16 p + 4 w .. 16 p + 4 w + 3 (w = 0 .. 3,
+ *       p = 0, 1) and adds them in increasing l: part_w = fmaf(scale_l, t_d, part_w);  the four parts cross the waves through
+ *       LDS and grad_x[row][d] = ((part_0 + part_1) + part_2) + part_3.  No atomics: bit-reproducible.
+ *   Rows past N neither read nor add.  Every idx is reduced modulo the level's entry count as in the forward: no input value
+ *   can make the kernel read or write outside the table.  N == 0: grad_table is set to zero, nothing is launched.
+ * Refused, nothing written: an unsupported option (VSX_E_UNSUPPORTED, K14's and K13's words); saved, scratch or grad shorter
+ *   than the workspace query says (VSX_E_WORKSPACE); a null pointer, a table, grad_table or saved that is not 16-byte
+ *   aligned, a table or a packed buffer of another length (VSX_E_BADSHAPE).
+ * ------------------------------------------------------------------------------------------ */
+int vsx_hash_mlp_train_workspace(int64_t N, int64_t input_dim, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
+                                 int64_t base_resolution, double per_level_scale, int64_t output_dim, int64_t hidden_dim,
+                                 int64_t mlp_layers, int64_t skip_mask, int64_t* saved_floats, int64_t* scratch_floats,
+                                 int64_t* grad_floats);
+int vsx_hash_mlp_fwd_train_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                               int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                               double per_level_scale, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers,
+                               int64_t skip_mask, int64_t use_tanh, const float* packed, int64_t packed_floats, float* out,
+                               float* saved, int64_t saved_floats, vsx_stream_t stream);
+int vsx_hash_mlp_bwd_f32(const float* grad_out, const float* x, int64_t N, int64_t input_dim, const float* table,
+                         int64_t table_floats, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
+                         int64_t base_resolution, double per_level_scale, int64_t output_dim, int64_t hidden_dim,
+                         int64_t mlp_layers, int64_t skip_mask, int64_t use_tanh, const float* packed, int64_t packed_floats,
+                         const float* saved, int64_t saved_floats, float* scratch, int64_t scratch_floats, float* grad,
+                         int64_t grad_floats, float* grad_table, float* grad_x, vsx_stream_t stream);
+int vsx_hash_grid_bwd_f32(const float* x, int64_t N, int64_t input_dim, const float* grad_enc, const float* table,
+                          int64_t table_floats, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
+                          int64_t base_resolution, double per_level_scale, float* grad_table, float* grad_x,
+                          vsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@
 // A workgroup runs as blockDim.x OS threads (blocks one after the other); __syncthreads is a std::barrier over the
 // workgroup, __shfl_xor an exchange through a per-wave scratch array between two wave barriers (all 64 lanes of a wave
 // must call it, as on the hardware), __shared__ is static storage (one workgroup is alive at a time).
-// atomicMax on a 32-bit word is a compare-exchange loop on std::atomic_ref (csrc/atlas_edit.hip's mask updates).
+// atomicMax on a 32-bit word is a compare-exchange loop on std::atomic_ref (csrc/atlas_edit.hip's mask updates), and so is
+// atomicAdd on a float (csrc/atlas_bwd.hip's table gradient).
 // Used by tools/cpu_check/check_*.cpp only (with hip_gemm.h for the MFMA / LDS-DMA kernels); never part of a library.
 #pragma once
 #include <math.h>
@@ -82,6 +83,14 @@ static inline unsigned atomicMax(unsigned* address, unsigned value) {
     std::atomic_ref<unsigned> ref(*address);
     unsigned old = ref.load(std::memory_order_relaxed);
     while (old < value && !ref.compare_exchange_weak(old, value, std::memory_order_relaxed)) {
+    }
+    return old;
+}
+// atomicAdd on a float of "global" memory (csrc/atlas_bwd.hip's table gradient): a compare-exchange loop; returns the old value
+static inline float atomicAdd(float* address, float value) {
+    std::atomic_ref<float> ref(*address);
+    float old = ref.load(std::memory_order_relaxed);
+    while (!ref.compare_exchange_weak(old, old + value, std::memory_order_relaxed)) {
     }
     return old;
 }

@@ -145,6 +145,14 @@ PROTOTYPES = {
     'vsx_coord_mlp_fwd_train_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                                                           c_void_p]),
     'vsx_coord_mlp_bwd_f32': (c_int, [c_void_p] + [c_int64] * 10 + [c_void_p, c_int64] * 4 + [c_void_p]),
+    # gradients of the hash-grid network: table, layers, input (csrc/atlas_bwd.hip, K17; the training forward in atlas.hip)
+    'vsx_hash_mlp_train_workspace': (c_int, [c_int64] * 6 + [c_double] + [c_int64] * 4 + [c_void_p] * 3),
+    'vsx_hash_mlp_fwd_train_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double] + [c_int64] * 5
+                                   + [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    'vsx_hash_mlp_bwd_f32': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p] + [c_int64] * 5 + [c_double] + [c_int64] * 5
+                             + [c_void_p, c_int64] * 4 + [c_void_p] * 3),
+    'vsx_hash_grid_bwd_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p] + [c_int64] * 5 + [c_double]
+                              + [c_void_p] * 3),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

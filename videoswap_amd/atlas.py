@@ -15,8 +15,10 @@ tiny-cuda-nn algorithm and has NOT been compared with tinycudann (DESIGN.md §11
 texture-reading half of evaluate_model (:344-419): the video re-rendered from EDITED texture images through `ops.atlas_edit`
 (csrc/atlas_edit.hip).  Fitting (videoswap_amd/atlas_fit.py): a `CoordMLP` switched on with
 `differentiable_(True)` has weight and bias gradients (csrc/atlas_bwd.hip), which is what mapping pre-training
-(`pretrain_mapping`) and the inverse-mapping fit (`fit_inverse_mapping`) need; both are in scope.  Full atlas training
-(train_atlas.py: the gradients of the hash grid and of F_Atlas's input, the losses) is not.
+(`pretrain_mapping`) and the inverse-mapping fit (`fit_inverse_mapping`) need; a `HashGridMLP` switched on the same way
+has gradients for its grid table, its layers and its input, which carries the reconstruction half of the
+training step (`reconstruction_losses`, `fit_reconstruction`).  The gradient, rigidity and flow losses of train_atlas.py,
+the optical flows of its data loading and train_atlas.py as a drop-in are not in scope.
 """
 import json
 import math
@@ -321,6 +323,14 @@ class HashGridMLP(_LayerStack):
         self.grid = grid
         self.encoder = _HashGridParams(hash_grid_floats(grid))           # before the layers: its place in the state dict
         self._build_hidden(int(grid['n_levels']) * int(grid['n_features_per_level']))
+        self._differentiable = False
+
+    def differentiable_(self, flag=True):
+        """Switch the gradient path on (off by default) -> self.  On, and while grad mode is on and a parameter or the
+        input requires grad, `forward` records gradients for the grid table, the layers and the input
+        (atlas_fit.HashGridMLPFunction).  The table's gradient is not bit-reproducible from run to run (fp32 atomics)."""
+        self._differentiable = bool(flag)
+        return self
 
     def load_state_dict(self, state_dict, *args, **kwargs):
         from . import formats
@@ -334,6 +344,9 @@ class HashGridMLP(_LayerStack):
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     def _launch(self, x):
+        if self._differentiable and torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in self.parameters())):
+            from .atlas_fit import differentiable_hash_forward
+            return differentiable_hash_forward(self, x)
         return ops.hash_mlp(x, self.encoder.params.detach(), self.grid, self.packed(), self.output_dim, self.hidden_dim,
                             self.mlp_layers, skip_layers=self.skip_layers, use_tanh=self.use_tanh)
 
@@ -556,4 +569,5 @@ def checkerboard_videos(models, res_x, res_y, number_of_frames, area_fg, area_bg
     return dict(checkerboard_fg=cfg, checkerboard_bg=cbg, texture_fg=texs[0], texture_bg=texs[1], launches=out['launches'] + 2)
 
 
-from .atlas_fit import fit_inverse_mapping, load_mask_frames, pretrain_mapping  # noqa: E402,F401  (the fitting half)
+from .atlas_fit import (fit_inverse_mapping, fit_reconstruction, load_mask_frames, pretrain_mapping,  # noqa: E402,F401
+                        reconstruction_losses)                                                   # (the fitting half)

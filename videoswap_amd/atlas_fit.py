@@ -1,13 +1,19 @@
-"""Fitting the mapping networks of a layered neural atlas: the gradient path of `CoordMLP` and the two steps of the
-reference that need nothing else.
+"""Fitting the networks of a layered neural atlas: the gradient paths of `CoordMLP` and `HashGridMLP`, the two steps of
+the reference that need only the first, and the reconstruction half of its training step, which needs both.
 
 `CoordMLP.differentiable_(True)` routes `forward` through `CoordMLPFunction`: `ops.coord_mlp_train_forward` (the forward
 kernel, storing its activations) and `ops.coord_mlp_backward` (csrc/atlas_bwd.hip: weight and bias gradients, fp32,
 deterministic).  There is no gradient with respect to the input: in train_atlas.py every coordinate network is fed data
-coordinates (the inverse's `uv` is computed under no_grad, :257-261); only the hash-grid network F_Atlas needs one, and
-that, with the atlas losses, is the half of atlas training that stays out of scope.
+coordinates (the inverse's `uv` is computed under no_grad, :257-261); only the hash-grid network F_Atlas needs one.
 
-`pretrain_mapping` restates videoswap/atlas/unwrap_utils.py:115-138, `fit_inverse_mapping` train_atlas.py:255-266.
+`HashGridMLP.differentiable_(True)` routes `forward` through `HashGridMLPFunction`: `ops.hash_mlp_train_forward` and
+`ops.hash_mlp_backward`: gradients for the grid table `encoder.params`, the layers and the input uv, which
+reaches the mapping networks through their outputs.  The table's gradient is a scatter-add with fp32 atomics and is not
+bit-reproducible from run to run; everything else is.
+
+`pretrain_mapping` restates videoswap/atlas/unwrap_utils.py:115-138, `fit_inverse_mapping` train_atlas.py:255-266,
+`reconstruction_losses` / `fit_reconstruction` train_atlas.py:135-162, 180-196 (the rgb, alpha and sparsity losses).  The
+gradient loss, the rigidity and flow losses and the optical flows they read are not implemented.
 """
 import os
 
@@ -49,6 +55,40 @@ def differentiable_forward(module, x):
         raise NotImplementedError('CoordMLP: input gradients are not implemented (the mapping networks of an atlas take data '
                                   'coordinates; only weight and bias gradients exist)')
     return CoordMLPFunction.apply(x, module, *(q for lin in module.hidden for q in (lin.weight, lin.bias)))
+
+
+class HashGridMLPFunction(torch.autograd.Function):
+    """y = module(x) of a HashGridMLP with gradients for x, for the grid table and for the layers (`table` and `params` are
+    passed so that autograd sees them); one ops call forward, one backward, whatever the number of rows.  grad_x is computed
+    only when x needs it, the table's gradient only when the table does."""
+
+    @staticmethod
+    def forward(ctx, x, table, module, *params):
+        packed = module.packed()
+        ctx.grid = dict(module.grid)
+        ctx.net = dict(output_dim=module.output_dim, hidden_dim=module.hidden_dim, mlp_layers=module.mlp_layers,
+                       skip_layers=tuple(module.skip_layers), use_tanh=module.use_tanh)
+        ctx.shapes = [tuple(q.shape) for q in params]
+        x, table = x.detach(), table.detach()
+        out, saved = ops.hash_mlp_train_forward(x, table, ctx.grid, packed, **ctx.net)
+        ctx.save_for_backward(x, table, saved, packed)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, table, saved, packed = ctx.saved_tensors
+        grad, grad_table, grad_x = ops.hash_mlp_backward(grad_out.contiguous(), x, table, ctx.grid, saved, packed, **ctx.net,
+                                                         want_table=ctx.needs_input_grad[1], want_x=ctx.needs_input_grad[0])
+        views, off = [], 0
+        for shape in ctx.shapes:
+            n = int(np.prod(shape))
+            views.append(grad[off:off + n].view(shape))
+            off += n
+        return (grad_x, grad_table, None, *views)
+
+
+def differentiable_hash_forward(module, x):
+    return HashGridMLPFunction.apply(x, module.encoder.params, module, *(q for lin in module.hidden for q in (lin.weight, lin.bias)))
 
 
 def _norm_funcs(res_x, res_y, number_of_frames):
@@ -176,3 +216,80 @@ def fit_inverse_mapping(FG_UV_Mapping, FG_UV_Mapping_Inverse, select, res_x, res
             mean_px, max_px = float(err.mean()), float(err.max())
     return dict(loss_history=history, steps_skipped=skipped, holdout_rows=int(xyt.shape[0]), roundtrip_mean_px=mean_px,
                 roundtrip_max_px=max_px)
+
+
+# ------------------------------------------------------------------------------------------------
+# the reconstruction half of the training step (train_atlas.py:135-162, 180-196)
+# ------------------------------------------------------------------------------------------------
+NETWORKS = ('FG_UV_Mapping', 'BG_UV_Mapping', 'F_Alpha', 'F_Atlas')
+# loss_cfg of the reference's atlas YAMLs, the three weights this half reads
+LOSS_CFG = {'reconstruction_loss': {'rgb_loss_weight': 5000.0, 'alpha_loss_weight': 2000.0},
+            'sparsity_loss': {'sparsity_loss_weight': 1000.0}}
+
+
+def reconstruction_losses(models, xyt, rgb, alpha_gt, loss_cfg=None, with_alpha_loss=True):
+    """train_atlas.py:147-162, 180-196 without get_gradient_loss -> (loss_total, loss_dict): xyt [n, 3] normalised pixel
+    coordinates, rgb [n, 3] their colours, alpha_gt [n, 1] their mask values; `loss_cfg`: train.loss_cfg of the atlas YAML
+    (default: the reference's weights); rgb_loss, alpha_loss (`with_alpha_loss`: the reference adds it while global_step
+    <= pretrain_alpha_iter) and sparsity_loss, alpha mapped to 0.001 .. 0.991 as there.  F_Atlas is evaluated ONCE on the
+    foreground and background queries together, as render_atlas does."""
+    from .atlas import _atlas_colours, _mappings_and_alpha
+    loss_cfg = LOSS_CFG if loss_cfg is None else loss_cfg
+    uv_fg, uv_bg, alpha = _mappings_and_alpha(models, xyt)
+    rgb_output_fg, rgb_output_bg = _atlas_colours(models['F_Atlas'], uv_fg, uv_bg)
+    rgb_output = rgb_output_fg * alpha + rgb_output_bg * (1.0 - alpha)
+    loss_dict = {}
+    rgb_loss = (torch.norm(rgb_output - rgb, dim=1) ** 2).mean()
+    loss_dict['rgb_loss'] = rgb_loss
+    loss_total = loss_cfg['reconstruction_loss']['rgb_loss_weight'] * rgb_loss
+    if with_alpha_loss:
+        alpha_loss = torch.mean(-alpha_gt * torch.log(alpha) - (1 - alpha_gt) * torch.log(1 - alpha))
+        loss_dict['alpha_loss'] = alpha_loss
+        loss_total = loss_total + loss_cfg['reconstruction_loss']['alpha_loss_weight'] * alpha_loss
+    rgb_loss_sparsity = (torch.norm(rgb_output_fg * (1.0 - alpha), dim=1) ** 2).mean()
+    loss_dict['sparsity_loss'] = rgb_loss_sparsity
+    loss_total = loss_total + loss_cfg['sparsity_loss']['sparsity_loss_weight'] * rgb_loss_sparsity
+    loss_dict['total_loss'] = loss_total
+    return loss_total, loss_dict
+
+
+def fit_reconstruction(models, video_frames, mask_frames, iters, batch=10000, lr=1e-4, train=('F_Atlas',), alpha_loss_iters=None,
+                       loss_cfg=None):
+    """The reconstruction half of the training loop: video_frames [H, W, 3, T] in [0, 1] and mask_frames [H, W, T] as
+    load_input_data holds them (on the CPU, like the reference's), `iters` steps of the reference's sampling
+    (train_atlas.py:135-145: one torch.randint over the (frame, row, column) order of get_tuples on the CPU default
+    generator, `batch` pixels), `reconstruction_losses`, and ONE Adam(lr) over the networks named in `train` (any of
+    FG_UV_Mapping, BG_UV_Mapping, F_Alpha, F_Atlas; the others stay as they are, bit for bit).  With a mapping network in
+    `train`, F_Atlas's input gradient drives it.  The alpha loss is added in the steps <= alpha_loss_iters (None: all).
+    -> the loss history (total_loss per step)."""
+    unknown = [k for k in train if k not in NETWORKS]
+    if unknown or not train:
+        raise ValueError(f'fit_reconstruction: train {tuple(train)} must name some of {NETWORKS}')
+    H, W, _, T = video_frames.shape
+    _, norm_s, norm_t = _norm_funcs(W, H, T)
+    device = next(models['F_Atlas'].parameters()).device
+    before = {k: [q.requires_grad for q in models[k].parameters()] for k in NETWORKS}
+    for k in NETWORKS:
+        models[k].requires_grad_(k in train)
+    optimizer = torch.optim.Adam([q for k in train for q in models[k].parameters()], lr=lr)
+    history = []
+    try:
+        with _Differentiable(*(models[k] for k in NETWORKS)):
+            for step in range(int(iters)):
+                idx = torch.randint(T * H * W, (int(batch), 1))
+                f, rem = idx // (H * W), idx % (H * W)
+                i, j = rem // W, rem % W
+                rgb = video_frames[i, j, :, f].squeeze(1).to(device=device, dtype=torch.float32)
+                alpha_gt = mask_frames[i, j, f].squeeze(1).to(device=device, dtype=torch.float32).unsqueeze(-1)
+                xyt = torch.cat([norm_s(j), norm_s(i), norm_t(f)], dim=1).to(device)
+                loss, _ = reconstruction_losses(models, xyt, rgb, alpha_gt, loss_cfg,
+                                                with_alpha_loss=alpha_loss_iters is None or step <= alpha_loss_iters)
+                optimizer.zero_grad()
+                loss.backward()
+                optimizer.step()
+                history.append(loss.item())
+    finally:
+        for k in NETWORKS:
+            for q, flag in zip(models[k].parameters(), before[k]):
+                q.requires_grad_(flag)
+    return history

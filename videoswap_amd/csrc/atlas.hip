@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "coord_mlp.h"
+#include "hash_grid.h"
 
 namespace {
 
@@ -41,30 +42,9 @@ struct CoordMlpParams {
     int w_off[CM_MAX_LAYERS], b_off[CM_MAX_LAYERS];   // in floats, multiples of 4
 };
 
-constexpr int HG_MAX_LEVELS = 32;
-constexpr int HG_PASS = 16;          // levels per pass of a workgroup: 4 waves x 4 levels per thread
-
-struct HgLevel {
-    float scale;                     // grid cells per unit, minus the half-cell shift's 1
-    uint32_t res, entries, offset;   // offset: first entry of the level in the table
-    uint32_t hashed;                 // 0: dense index g0 + g1 * res, 1: spatial hash
-};
-
-struct HashGrid {
-    static constexpr bool kHash = true;
-    const float2* table;             // [sum entries][2 features], level-major
-    int n_levels;
-    HgLevel lv[HG_MAX_LEVELS];       // unused levels: entries 1, never read from the table
-};
-
-struct NoGrid {
-    static constexpr bool kHash = false;
-};
-
 // The two features of the levels l0 .. l0 + 3 at (x0, x1): f[j] = sum over the four corners of the cell, in corner order,
-// of weight * table entry.  All index arithmetic is uint32 with wrap-around; every index is reduced modulo the level's
-// entry count, so no coordinate (negative, huge, NaN) can address outside the table.  `ok` false (row past N) or a level
-// past n_levels: nothing is gathered, the features are zero.  The 16 eight-byte loads are issued before the first use.
+// of weight * table entry; the cell, its entries and its weights are hg_cell's (hash_grid.h).  `ok` false (row past N) or a
+// level past n_levels: nothing is gathered, the features are zero.  The 16 eight-byte loads are issued before the first use.
 __device__ __forceinline__ void hg_encode4(const HashGrid& g, int l0, bool ok, float x0, float x1, float2 (&f)[4]) {
     float2 v[4][4];
     float w0[4], w1[4];
@@ -73,24 +53,17 @@ __device__ __forceinline__ void hg_encode4(const HashGrid& g, int l0, bool ok, f
         const int l = l0 + j;
         const HgLevel lv = g.lv[l & (HG_MAX_LEVELS - 1)];
         const bool use = ok && l < g.n_levels;
-        const float p0 = fmaf(lv.scale, x0, 0.5f), p1 = fmaf(lv.scale, x1, 0.5f);
-        const float fl0 = floorf(p0), fl1 = floorf(p1);
-        const uint32_t g0 = (uint32_t)(int)fl0, g1 = (uint32_t)(int)fl1;
-        w0[j] = p0 - fl0, w1[j] = p1 - fl1;
+        uint32_t idx[4];
+        hg_cell(lv, x0, x1, w0[j], w1[j], idx);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const uint32_t c0 = g0 + (c & 1), c1 = g1 + (c >> 1);
-            uint32_t idx = lv.hashed ? (c0 ^ (c1 * 2654435761u)) : c0 + c1 * lv.res;
-            idx %= lv.entries;
-            v[j][c] = use ? g.table[lv.offset + idx] : float2{0.f, 0.f};
-        }
+        for (int c = 0; c < 4; ++c) v[j][c] = use ? g.table[idx[c]] : float2{0.f, 0.f};
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float a = 0.f, b = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const float w = ((c & 1) ? w0[j] : 1.f - w0[j]) * ((c >> 1) ? w1[j] : 1.f - w1[j]);
+            const float w = hg_weight(c, w0[j], w1[j]);
             a = fmaf(w, v[j][c].x, a), b = fmaf(w, v[j][c].y, b);
         }
         f[j] = float2{a, b};
@@ -161,11 +134,10 @@ __device__ __forceinline__ void cm_layer(f16v (&acc)[2][2], const CoordMlpParams
     if (kbe) cm_accumulate<NF, NR, S>(acc, wl, kbh + kbe, kbh, kbe, enc, ft, rt0, lane);
 }
 
-// Train: the same arithmetic, and every row < N also stores what the backward reads (vsx.h K16): the encoded input, every
-// hidden layer's activation after its ReLU, and the output.
+// Train: the same arithmetic, and every row < N also stores what the backward reads (vsx.h K16 / K17): the encoded input
+// (behind the hash grid: the two features of every level), every hidden layer's activation after its ReLU, and the output.
 template <class Grid, bool Train = false>
 __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpParams p, const Grid g) {
-    static_assert(!(Train && Grid::kHash), "the hash grid has no backward");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     f4v* act = reinterpret_cast<f4v*>(smem);                       // [hidden / 4][CM_BM]
     f4v* enc = act + (p.hidden / 4) * CM_BM;                       // [encp / 4][CM_BM]
@@ -185,6 +157,10 @@ __global__ __launch_bounds__(CM_THREADS) void coord_mlp_kernel(const CoordMlpPar
             for (int j = 0; j < 4; ++j) {
                 const int e = 2 * (l0 + 4 * wl + j);
                 if (e < p.encp) *reinterpret_cast<float2*>(reinterpret_cast<float*>(enc) + ((e >> 2) * CM_BM + r) * 4 + (e & 3)) = f[j];
+                if constexpr (Train) {
+                    if (ok && e < p.enc)
+                        *reinterpret_cast<float2*>(p.saved + (long)(p.layers - 1) * p.N * p.hidden + (row0 + r) * p.enc + e) = f[j];
+                }
             }
         }
     } else {
@@ -346,56 +322,6 @@ int cm_launch(const char* what, const CoordMlpParams& p, const Grid& g, vsx_stre
     return vsx_check_launch(what);
 }
 
-// THE definition of the level geometry (tiny-cuda-nn's GridEncoding constructor, restated): per level l
-//   scale = exp2f(l * log2f(per_level_scale)) * base_resolution - 1   (fp32),   res = (uint32)ceilf(scale) + 1,
-//   entries = min(round_up(res^2, 8), 2^log2_hashmap_size),   offset = the running sum of entries,
-// and the index of a corner (g0, g1), uint32 with wrap-around: stride = 1; idx = g0, stride *= res; then, while
-// stride <= entries, idx += g1 * stride, stride *= res; the level is HASHED when entries < stride afterwards.
-// Returns the table's float count, or a negative VSX_E_* (the message names the option).
-int64_t hg_geometry(const char* what, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
-                    int64_t base_resolution, double per_level_scale, HgLevel* lv) {
-    VSX_REQUIRE(n_features == 2, VSX_E_UNSUPPORTED, "%s: n_features_per_level %lld (only 2)", what, (long long)n_features);
-    VSX_REQUIRE(n_levels >= 1 && n_levels <= HG_MAX_LEVELS && n_levels * n_features <= CM_MAX_ENC, VSX_E_UNSUPPORTED,
-                "%s: n_levels %lld (1 to %d, at most %d encoded columns)", what, (long long)n_levels, HG_MAX_LEVELS, CM_MAX_ENC);
-    VSX_REQUIRE(log2_hashmap_size >= 3 && log2_hashmap_size <= 24, VSX_E_UNSUPPORTED, "%s: log2_hashmap_size %lld (3 to 24)",
-                what, (long long)log2_hashmap_size);
-    VSX_REQUIRE(base_resolution >= 1 && base_resolution <= 65536, VSX_E_UNSUPPORTED, "%s: base_resolution %lld (1 to 65536)",
-                what, (long long)base_resolution);
-    VSX_REQUIRE(per_level_scale >= 1.0 && per_level_scale <= 16.0, VSX_E_UNSUPPORTED, "%s: per_level_scale %g (1 to 16)", what,
-                per_level_scale);
-    const uint32_t cap = 1u << log2_hashmap_size;
-    uint64_t offset = 0;
-    for (int l = 0; l < HG_MAX_LEVELS; ++l) {
-        lv[l] = HgLevel{0.f, 1u, 1u, 0u, 0u};
-        if (l >= n_levels) continue;
-        const float scale = exp2f((float)l * log2f((float)per_level_scale)) * (float)base_resolution - 1.0f;
-        // inputs lie within [-2, 2]: 2 * scale + 1.5 must stay far inside int32 for (uint32)(int)floorf(pos)
-        VSX_REQUIRE(scale >= 0.f && scale <= 16777216.f, VSX_E_UNSUPPORTED,
-                    "%s: per_level_scale %g / base_resolution %lld: level %d has %g cells (at most 2^24)", what, per_level_scale,
-                    (long long)base_resolution, l, (double)scale);
-        const uint32_t res = (uint32_t)ceilf(scale) + 1u;
-        const uint64_t dense = ((uint64_t)res * res + 7) / 8 * 8;
-        const uint32_t entries = dense < cap ? (uint32_t)dense : cap;
-        uint32_t stride = res;                                   // after dimension 0 (stride 1 <= entries always)
-        if (stride <= entries) stride *= res;                    // dimension 1, uint32 wrap-around
-        lv[l] = HgLevel{scale, res, entries, (uint32_t)offset, entries < stride ? 1u : 0u};
-        offset += entries;
-    }
-    return (int64_t)offset * n_features;
-}
-
-int hg_fill(const char* what, HashGrid& g, int64_t input_dim, const float* table, int64_t table_floats, int64_t n_levels,
-            int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution, double per_level_scale) {
-    VSX_REQUIRE(input_dim == 2, VSX_E_UNSUPPORTED, "%s: input_dim %lld (the hash grid is implemented for 2 only)", what,
-                (long long)input_dim);
-    const int64_t need = hg_geometry(what, n_levels, n_features, log2_hashmap_size, base_resolution, per_level_scale, g.lv);
-    if (need < 0) return (int)need;
-    VSX_REQUIRE(table_floats == need, VSX_E_BADSHAPE, "%s: the grid table holds %lld floats, this configuration needs %lld", what,
-                (long long)table_floats, (long long)need);
-    g.table = reinterpret_cast<const float2*>(table), g.n_levels = (int)n_levels;
-    return VSX_OK;
-}
-
 }  // namespace
 
 extern "C" int vsx_coord_mlp_f32(const float* x, int64_t N, int64_t input_dim, int64_t output_dim, int64_t hidden_dim,
@@ -481,4 +407,28 @@ extern "C" int vsx_hash_mlp_f32(const float* x, int64_t N, int64_t input_dim, co
                                use_tanh, packed, packed_floats, out);
     if (prc != VSX_OK || N == 0) return prc;
     return cm_launch("vsx_hash_mlp_f32", p, g, stream);
+}
+
+// K17, the forward half: vsx_hash_mlp_f32 with the stores of the training instantiation
+extern "C" int vsx_hash_mlp_fwd_train_f32(const float* x, int64_t N, int64_t input_dim, const float* table, int64_t table_floats,
+                                          int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size, int64_t base_resolution,
+                                          double per_level_scale, int64_t output_dim, int64_t hidden_dim, int64_t mlp_layers,
+                                          int64_t skip_mask, int64_t use_tanh, const float* packed, int64_t packed_floats, float* out,
+                                          float* saved, int64_t saved_floats, vsx_stream_t stream) {
+    HashGrid g;
+    const int rc = hg_fill("hash_mlp_fwd_train", g, input_dim, table, table_floats, n_levels, n_features, log2_hashmap_size,
+                           base_resolution, per_level_scale);
+    if (rc != VSX_OK) return rc;
+    VSX_REQUIRE(N <= 0 || table, VSX_E_BADSHAPE, "hash_mlp_fwd_train: null argument");
+    VSX_REQUIRE(N <= 0 || vsx_aligned16(table), VSX_E_BADSHAPE, "hash_mlp_fwd_train: the grid table must be 16-byte aligned");
+    CoordMlpParams p;
+    const int prc = cm_prepare("hash_mlp_fwd_train", p, x, N, 2, output_dim, hidden_dim, mlp_layers, 0, n_levels * n_features,
+                               skip_mask, use_tanh, packed, packed_floats, out);
+    if (prc != VSX_OK || N == 0) return prc;
+    VSX_REQUIRE(saved && vsx_aligned16(saved), VSX_E_BADSHAPE, "hash_mlp_fwd_train: saved must be a 16-byte aligned buffer");
+    const int64_t need = cm_saved_floats(N, n_levels * n_features, output_dim, hidden_dim, mlp_layers);
+    VSX_REQUIRE(saved_floats >= need, VSX_E_WORKSPACE, "hash_mlp_fwd_train: saved holds %lld floats, N = %lld needs %lld",
+                (long long)saved_floats, (long long)N, (long long)need);
+    p.saved = saved;
+    return cm_launch<HashGrid, true>("vsx_hash_mlp_fwd_train_f32", p, g, stream);
 }

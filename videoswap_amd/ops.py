@@ -1009,6 +1009,95 @@ def hash_mlp(x, table, grid, packed, output_dim, hidden_dim, mlp_layers, skip_la
     return out
 
 
+def _hash_net(output_dim, hidden_dim, mlp_layers, skip_layers, what):
+    return int(output_dim), int(hidden_dim), int(mlp_layers), _skip_mask(skip_layers, what)
+
+
+def hash_grid_backward(x, grad_enc, table, grid, want_table=True, want_x=True):
+    """The gradients of `hash_grid` alone (include/vsx.h K17): x fp32 [N, 2], grad_enc fp32 [N, n_levels *
+    n_features_per_level] -> (grad_table, grad_x): fp32 flat like `table` / fp32 [N, 2]; None where not wanted.  grad_x is
+    deterministic; grad_table is a scatter-add with fp32 atomics and is NOT bit-reproducible from run to run."""
+    d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_grid_backward')
+    _chk(grad_enc, 'grad_enc', torch.float32)
+    if grad_enc.dim() != 2 or tuple(grad_enc.shape) != (x.shape[0], cfg[0] * cfg[1]):
+        raise _lib.VsxError(f'hash_grid_backward: grad_enc must be [{x.shape[0]}, {cfg[0] * cfg[1]}], got {tuple(grad_enc.shape)}')
+    grad_table = torch.empty_like(table) if want_table else None
+    grad_x = torch.empty_like(x) if want_x else None
+    rc = _lib.load().vsx_hash_grid_bwd_f32(_p(x), x.shape[0], d, _p(grad_enc), tab, floats, *cfg, _p(grad_table), _p(grad_x),
+                                           _stream())
+    _check_supported(rc, 'vsx_hash_grid_bwd_f32')
+    return grad_table, grad_x
+
+
+def hash_mlp_train_workspace(N, grid, output_dim, hidden_dim, mlp_layers, skip_layers=(), input_dim=2):
+    """-> (saved, scratch, grad): the float counts of the three buffers of a training step of `hash_mlp` over N rows
+    (vsx.h K17; grad covers the layers only)"""
+    counts = [ctypes.c_int64(0) for _ in range(3)]
+    rc = _lib.load().vsx_hash_mlp_train_workspace(
+        int(N), int(input_dim), int(grid['n_levels']), int(grid['n_features_per_level']), int(grid['log2_hashmap_size']),
+        int(grid['base_resolution']), float(grid['per_level_scale']),
+        *_hash_net(output_dim, hidden_dim, mlp_layers, skip_layers, 'hash_mlp_train_workspace'),
+        *(ctypes.addressof(c) for c in counts))
+    _check_supported(rc, 'vsx_hash_mlp_train_workspace')
+    return tuple(int(c.value) for c in counts)
+
+
+def hash_mlp_train_forward(x, table, grid, packed, output_dim, hidden_dim, mlp_layers, skip_layers=(), use_tanh=True, saved=None):
+    """`hash_mlp` (the same kernel source, the same bits) that also stores what `hash_mlp_backward` reads -> (out, saved):
+    saved fp32, flat (vsx.h K17: the hidden activations after their ReLU, the grid's features, out).  `saved`: a buffer to
+    fill instead of a new one; one shorter than `hash_mlp_train_workspace` says is refused (VsxError)."""
+    d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_mlp_train_forward')
+    _chk(packed, 'packed', torch.float32)
+    _chk(saved, 'saved', torch.float32)
+    net = _hash_net(output_dim, hidden_dim, mlp_layers, skip_layers, 'hash_mlp_train_forward')
+    lib = _lib.load()
+    if saved is None:
+        n_saved = ctypes.c_int64(0)
+        _check_supported(lib.vsx_hash_mlp_train_workspace(x.shape[0], d, *cfg, *net, ctypes.addressof(n_saved), None, None),
+                         'vsx_hash_mlp_train_workspace')
+        saved = torch.empty(n_saved.value, dtype=torch.float32, device=x.device)
+    out = torch.empty(x.shape[0], int(output_dim), dtype=torch.float32, device=x.device)
+    rc = lib.vsx_hash_mlp_fwd_train_f32(_p(x), x.shape[0], d, tab, floats, *cfg, *net, int(bool(use_tanh)), _p(packed),
+                                        packed.numel(), _p(out), _p(saved), saved.numel(), _stream())
+    _check_supported(rc, 'vsx_hash_mlp_fwd_train_f32')
+    return out, saved
+
+
+def hash_mlp_backward(grad_out, x, table, grid, saved, packed, output_dim, hidden_dim, mlp_layers, skip_layers=(), use_tanh=True,
+                      want_table=True, want_x=True, grad=None, scratch=None):
+    """The gradients of the network `hash_mlp_train_forward` ran: grad_out fp32 [N, output_dim]; x, table, `saved` and
+    `packed` of that call -> (grad, grad_table, grad_x): grad one flat fp32 buffer, per layer the weight gradient [out, in]
+    (nn.Linear layout, unpadded), then the bias gradient; grad_table flat like `table`; grad_x [N, 2]; the last two None
+    where not wanted.  grad and grad_x are deterministic (no atomics, fixed summation orders); grad_table is a scatter-add
+    with fp32 atomics and is NOT bit-reproducible from run to run (vsx.h K17).  `grad` / `scratch`: buffers to use instead
+    of new ones; a short `saved`, `scratch` or `grad` is refused (VsxError)."""
+    d, tab, floats, *cfg = _hash_grid_args(x, table, grid, 'hash_mlp_backward')
+    _chk(grad_out, 'grad_out', torch.float32)
+    _chk(saved, 'saved', torch.float32)
+    _chk(packed, 'packed', torch.float32)
+    _chk(grad, 'grad', torch.float32)
+    _chk(scratch, 'scratch', torch.float32)
+    N = x.shape[0]
+    if grad_out.dim() != 2 or tuple(grad_out.shape) != (N, int(output_dim)):
+        raise _lib.VsxError(f'hash_mlp_backward: grad_out must be [{N}, {output_dim}], got {tuple(grad_out.shape)}')
+    net = _hash_net(output_dim, hidden_dim, mlp_layers, skip_layers, 'hash_mlp_backward')
+    lib = _lib.load()
+    counts = [ctypes.c_int64(0) for _ in range(2)]
+    _check_supported(lib.vsx_hash_mlp_train_workspace(N, d, *cfg, *net, None, *(ctypes.addressof(c) for c in counts)),
+                     'vsx_hash_mlp_train_workspace')
+    if scratch is None:
+        scratch = torch.empty(counts[0].value, dtype=torch.float32, device=x.device)
+    if grad is None:
+        grad = torch.empty(counts[1].value, dtype=torch.float32, device=x.device)
+    grad_table = torch.empty_like(table) if want_table else None
+    grad_x = torch.empty_like(x) if want_x else None
+    rc = lib.vsx_hash_mlp_bwd_f32(_p(grad_out), _p(x), N, d, tab, floats, *cfg, *net, int(bool(use_tanh)), _p(packed),
+                                  packed.numel(), _p(saved), saved.numel(), _p(scratch), scratch.numel(), _p(grad), grad.numel(),
+                                  _p(grad_table), _p(grad_x), _stream())
+    _check_supported(rc, 'vsx_hash_mlp_bwd_f32')
+    return grad, grad_table, grad_x
+
+
 def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None, base_bg=None, masks=None):
     """The texture-reading half of evaluate_model in one launch (include/vsx.h K15): uv_fg, uv_bg fp32 [N, 2] (the mapping
     networks' outputs), alpha fp32 [N] (0.001 .. 0.991), a texture fp32 [R, R, 3 or 4] and its box (minx, miny, pixel_size:
@@ -1277,7 +1366,8 @@ _ACTIVATIONS = {
 _PLAIN = ('gemm', 'set_option', 'get_option', 'prof_pause', 'prof_enable', 'prof_collect', 'prof_collect_roofline', 'softmax_rows', 'geglu_fwd', 'geglu_bwd', 'silu_bwd',
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
-          'hash_mlp', 'atlas_edit', 'coord_mlp_train_workspace', 'coord_mlp_train_forward', 'coord_mlp_backward')
+          'hash_mlp', 'atlas_edit', 'coord_mlp_train_workspace', 'coord_mlp_train_forward', 'coord_mlp_backward',
+          'hash_grid_backward', 'hash_mlp_train_workspace', 'hash_mlp_train_forward', 'hash_mlp_backward')
 
 
 def _publish(name):
