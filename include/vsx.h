@@ -291,7 +291,8 @@ int vsx_unpack_latents(const void* x, void* y, int64_t B, int64_t Cout, int64_t 
 int vsx_cfg_ddim_step(const void* x, const void* eps_u, const void* eps_c, float guidance,
                       float alpha_t, float alpha_next, void* out, int64_t n, vsx_stream_t stream);
 /* Latent blend of the Prompt-to-Prompt SpatialBlender (spatial_blend.py:142):
- * out = src + mask*(x - src); mask fp16 broadcast over channels: x,src [C, n_sp], mask [n_sp]. */
+ * out = src + mask*(x - src); mask fp16 broadcast over channels: x,src [C, n_sp], mask [n_sp].
+ * A mask of exactly 0 returns src and a mask of exactly 1 returns x, bit for bit. */
 int vsx_masked_blend(const void* x, const void* src, const void* mask, void* out, int64_t C,
                      int64_t n_sp, vsx_stream_t stream);
 

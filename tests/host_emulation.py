@@ -234,8 +234,8 @@ def cfg_ddim_step(x, eps_u, eps_c, guidance, alpha_t, alpha_next):
 
 
 def masked_blend(x, src, mask):
-    a = src.float()
-    return (a + mask.float().reshape(1, *x.shape[1:]) * (x.float() - a)).to(H)
+    a, m = src.float(), mask.float().reshape(1, *x.shape[1:])
+    return torch.where(m == 1, x, (a + m * (x.float() - a)).to(H))          # a mask of 1 selects x, bit for bit
 
 
 def adapter_scatter(tracks, selected, feat, h, w, rate, out_scale=1.0):

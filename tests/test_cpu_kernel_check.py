@@ -130,7 +130,8 @@ def test_normalisation_kernels_run_on_the_cpu(tmp_path):
     """csrc/norm.hip from its real source on the host: GroupNorm statistics / finalize / apply (4-D and 5-D scopes, the two-source
     concat with groups that straddle the sources, SiLU, C = 2560), LayerNorm (three vector widths, temporal positional encoding),
     the row statistics of the LayerNorm fold, plain and causal row softmax — against double precision
-    (tools/cpu_check/check_norm.cpp)."""
+    (tools/cpu_check/check_norm.cpp).  Also the indexing edges of tests/norm_case.py (one channel per group, C = 8 / 520 / 4096,
+    64 and 65 chunks, LayerNorm at 512 / 520 / 1024 / 1032, one row per frame) and one GroupNorm whose mean dwarfs its spread."""
     cxx = CXX if os.path.isfile(CXX) else shutil.which('clang++')
     src = os.path.join(ROOT, 'tools', 'cpu_check')
     exe = str(tmp_path / 'check_norm')

@@ -8,7 +8,10 @@ The kernels of the training step (csrc/train.hip: GEGLU, SiLU, GroupNorm, LayerN
 adapter_gather) and quick_gelu, silu and the two row softmaxes have their parity tests in tests/test_train_kernels_gpu.py:
 each on its own against fp64, with bounds taken from the fp32 ideal on the same inputs.  The attention kernels (flash forward
 and backward, temporal, the materialised path) are pinned the same way at tile-edge shapes in
-tests/test_attention_kernels_gpu.py; the attention tests below keep the model's own shapes.
+tests/test_attention_kernels_gpu.py; the attention tests below keep the model's own shapes.  The forward normalisation kernels
+(csrc/norm.hip: GroupNorm, LayerNorm, the row statistics and their combine, the folded LayerNorm) and the scalar glue of
+csrc/elementwise.hip are pinned against fp64 at their indexing edges, and up a ladder of inputs whose mean dwarfs their spread, in
+tests/test_norm_kernels_gpu.py; the norm and glue tests below keep the model's own shapes and their fixed tolerances.
 """
 import math
 

@@ -70,9 +70,13 @@ static std::vector<double> dbl(const std::vector<T>& v) {
 }
 
 // GroupNorm over [nimg, rows, C1 (+ C2)] (5-D scope: nimg = batch, rows = frames x pixels; 4-D: nimg = batch x frames)
-static void run_groupnorm(const char* name, long nimg, long rows, long C1, long C2, long groups, bool silu) {
+// (scale, shift: the first source is uniform in shift +- scale.  The reference below is one-pass in double, q / n - mean^2, which is
+// exact for these sizes: the kernels' fp32 cancellation IS in the comparison.  At mean / std = 57 it stays under the 2e-3 of
+// `report` (rel-L2 2.6e-4 against 2.0e-4 unshifted); tests/test_norm_kernels_gpu.py measures it rung by rung)
+static void run_groupnorm(const char* name, long nimg, long rows, long C1, long C2, long groups, bool silu, float scale = 1.5f,
+                          float shift = 0.4f) {
     const long C = C1 + C2, cpg = C / groups;
-    auto x1 = randh((size_t)nimg * rows * C1, 1.5f, 0.4f), x2 = randh((size_t)nimg * rows * (C2 ? C2 : 8), 0.7f, -0.2f);
+    auto x1 = randh((size_t)nimg * rows * C1, scale, shift), x2 = randh((size_t)nimg * rows * (C2 ? C2 : 8), 0.7f, -0.2f);
     auto gamma = randh(C, 0.3f, 1.0f), beta = randh(C, 0.2f);
     std::vector<double> want((size_t)nimg * rows * C);
     auto at = [&](long i, long r, long c) { return c < C1 ? (double)x1[(i * rows + r) * C1 + c] : (double)x2[(i * rows + r) * C2 + c - C1]; };
@@ -187,6 +191,20 @@ int main(int argc, char** argv) {
     if (only < 0 || only == 8) run_softmax("softmax rows 21 x 77 (ld 80)", 21, 77, 80, 0);
     if (only < 0 || only == 9) run_softmax("softmax rows 9 x 256", 9, 256, 256, 0);
     if (only < 0 || only == 10) run_softmax("causal softmax 2 x 12 rows x 12 (ld 16)", 24, 12, 16, 12);
+    // the indexing edges of tests/norm_case.py, so that the check before a GPU run walks the same paths
+    if (only < 0 || only == 11) run_groupnorm("GroupNorm one channel per group 2 x 33 x 64, 64 groups", 2, 33, 64, 0, 64, true);
+    if (only < 0 || only == 12) run_groupnorm("GroupNorm C = 8 (512 rows per pass), 5 rows", 1, 5, 8, 0, 1, false);
+    if (only < 0 || only == 13) run_groupnorm("GroupNorm C = 8, 4 images of one row", 4, 1, 8, 0, 2, true);
+    if (only < 0 || only == 14) run_groupnorm("GroupNorm C = 520 (455 threads: the last wave 7 lanes wide)", 2, 41, 520, 0, 8, true);
+    if (only < 0 || only == 15) run_groupnorm("GroupNorm C = 4096 (both LDS arrays full)", 1, 17, 4096, 0, 32, false);
+    if (only < 0 || only == 16) run_groupnorm("GroupNorm 512 rows x 32: 64 chunks (fused finalize's limit)", 1, 512, 32, 0, 8, false);
+    if (only < 0 || only == 17) run_groupnorm("GroupNorm 513 rows x 32: 65 chunks", 1, 513, 32, 0, 8, false);
+    if (only < 0 || only == 18) run_groupnorm("GroupNorm 2 x 100 x 320 shifted (uniform in 8 .. 8.5)", 2, 100, 320, 0, 32, false, 0.25f, 8.25f);
+    if (only < 0 || only == 19) run_layernorm("LayerNorm 9 x 512 (one vector per lane, full)", 9, 512, false, 0, 0, 0);
+    if (only < 0 || only == 20) run_layernorm("LayerNorm 9 x 520 (two vectors per lane, the second nearly empty)", 9, 520, false, 0, 0, 0);
+    if (only < 0 || only == 21) run_layernorm("LayerNorm 5 x 1024", 5, 1024, false, 0, 0, 0);
+    if (only < 0 || only == 22) run_layernorm("LayerNorm 5 x 1032", 5, 1032, false, 0, 0, 0);
+    if (only < 0 || only == 23) run_layernorm("LayerNorm + temporal PE 24 x 64 (one row per frame, 24 frames)", 24, 64, true, 1, 24, 0);
     printf(n_bad ? "%d check(s) FAILED\n" : "all checks passed\n", n_bad);
     return n_bad ? 1 : 0;
 }

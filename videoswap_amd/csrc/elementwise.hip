@@ -73,8 +73,10 @@ __global__ void masked_blend_kernel(const half_t* __restrict__ x, const half_t* 
     const long i = (long)blockIdx.x * EW_THREADS + threadIdx.x;
     if (i >= C * n_sp) return;
     const long s = i % n_sp;
-    const float a = (float)src[i];
-    out[i] = (half_t)(a + (float)mask[s] * ((float)x[i] - a));
+    const float a = (float)src[i], m = (float)mask[s];
+    // a mask of 1 SELECTS x (0 selects src by the arithmetic alone): src + 1 * (x - src) is x only up to the fp32 rounding of
+    // x - src, which is more than half an fp16 ulp of x where |x| < 2^-12 |src|
+    out[i] = m == 1.f ? x[i] : (half_t)(a + m * ((float)x[i] - a));
 }
 
 // One workgroup per (frame, point): the 4 corner splats of a point are applied sequentially by
