@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 15
+#define VSX_ABI_VERSION 16
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -142,6 +142,19 @@ int vsx_gemm_f16(const vsx_gemm_desc* d, vsx_stream_t stream);
    code), without launching anything and without touching the memory d points at.  A caller that can describe a launch in two forms asks
    before it builds what only one of them needs (videoswap_amd.ops.conv2d: upsample = 2, else the nine-tap form). */
 int vsx_gemm_check(const vsx_gemm_desc* d);
+/* ABI 16: WHICH kernel vsx_gemm_f16(d, stream) would launch under the current options: the same checks and the same plan again
+   (one piece of code), no HIP call, nothing d points at is read.  Returns the status of vsx_gemm_check(d) and writes
+     out[0] family: 0 weight-stationary K = 320 kernel, 1 persistent 256-row tiles, 2 persistent 128-row tiles, 3 a workgroup-per-tile
+            kernel; -1 where no plan was made (d fails the descriptor checks, or M == 0), the other seven are then 0
+     out[1], out[2] BM, BN: the tile (32 x 320 row blocks for family 0, 256 / 128 x 320 for families 1 / 2)
+     out[3] deep: the four-slot ring of the 128 x 160 tile
+     out[4], out[5] splits, nk_per: K slices (1 = no split-K) and 64-wide K slabs per slice (0 without a split); d->workspace decides as
+            in the launch (vsx_gemm_workspace says how much it takes)
+     out[6] stat_parts: vsx_gemm_rowstats_parts(d)
+     out[7] refused: 0, or why the launch is VSX_E_UNSUPPORTED although a kernel was chosen (1: the sub-pixel form off the persistent
+            kernel, 2: rowstats_parts is not what the launch writes).
+   For tests that aim a shape at one kernel's edge, and tools that report what ran. */
+int vsx_gemm_plan(const vsx_gemm_desc* d, int64_t out[8]);
 /* parts per row the launch described by d would write into d->rowstats (see above); the answer does not depend on
    d->rowstats / d->rowstats_parts themselves */
 int64_t vsx_gemm_rowstats_parts(const vsx_gemm_desc* d);

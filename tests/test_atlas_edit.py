@@ -405,4 +405,4 @@ def test_refusals_of_the_op_and_of_the_entry_point():
                                (dict(mask=out, mh=2, mw=4), -1, 'mask is 2 x 4'), (dict(tex=base + 4), -1, '16-byte aligned')):
         assert call(**kwargs) == code, kwargs
         assert word in lib.vsx_last_error().decode(), (kwargs, lib.vsx_last_error())
-    assert _lib.VSX_ABI_VERSION == 15 == lib.vsx_abi_version()
+    assert _lib.VSX_ABI_VERSION == lib.vsx_abi_version() >= 15       # (the entry point is ABI 15's)

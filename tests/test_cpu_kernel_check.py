@@ -113,8 +113,9 @@ def test_gemm_entry_point_runs_on_the_cpu(tmp_path):
     # first two blocks (either one loosened by the size of its shortening fails this run)
     # 25: the same kernel over column slices (N = 640 / 960) with the folded LayerNorm and the gathered row vector
     # 26: plan_gemm against the pinned table of tools/cpu_check/gemm_plan_rows.inc (every shape of the UNet's launch mix, both sides of
-    # every threshold, every option value that steers the choice), and vsx_gemm_workspace / vsx_gemm_rowstats_parts against the plan
-    for case, late in (('21', False), ('22', True), ('23', False), ('24', True), ('25', True), ('26', False)):
+    # every threshold, every option value that steers the choice), and vsx_gemm_workspace / vsx_gemm_rowstats_parts / vsx_gemm_plan against the plan
+    # 27: forced split counts that would leave the last K slice without a slab (plan_splitk takes slices away), through vsx_gemm_plan
+    for case, late in (('21', False), ('22', True), ('23', False), ('24', True), ('25', True), ('26', False), ('27', False)):
         r = subprocess.run([exe, case], capture_output=True, text=True, timeout=900,
                            env=dict(env, CPUHIP_DMA='late') if late else env)
         print('late DMA' if late else '', r.stdout)

@@ -12,6 +12,10 @@ tests/test_attention_kernels_gpu.py; the attention tests below keep the model's 
 (csrc/norm.hip: GroupNorm, LayerNorm, the row statistics and their combine, the folded LayerNorm) and the scalar glue of
 csrc/elementwise.hip are pinned against fp64 at their indexing edges, and up a ladder of inputs whose mean dwarfs their spread, in
 tests/test_norm_kernels_gpu.py; the norm and glue tests below keep the model's own shapes and their fixed tolerances.
+The GEMM and implicit-GEMM convolution kernels (csrc/gemm.hip, gemm_pp.hip: the tile kernels, split-K, the persistent and the
+weight-stationary kernels, both convolution loaders, the sub-pixel form, every epilogue) are pinned at their tile edges in
+tests/test_gemm_kernels_gpu.py: on small-integer inputs bit for bit against the fp64 result rounded once, inside guard bands, each
+case aimed at one kernel through vsx_gemm_plan; the GEMM tests below keep the model's own shapes and their fixed tolerances.
 """
 import math
 

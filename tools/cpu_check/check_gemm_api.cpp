@@ -378,6 +378,13 @@ static void check_plans() {
         // what the host asks before it chooses a form: the launch's own status, refused exactly where the plan is
         const int status = vsx_gemm_check(&d);
         ok = ok && status == (r.refused ? VSX_E_UNSUPPORTED : VSX_OK);
+        // the read-only query (vsx_gemm_plan) answers the same plan and the same status
+        int64_t q[8];
+        const int qrc = vsx_gemm_plan(&d, q);
+        ok = ok && qrc == status && q[0] == (int)plan.family && q[4] == plan.splits && q[5] == (plan.splits > 1 ? plan.nk_per : 0) &&
+             q[6] == plan.stat_parts && q[7] == (int)plan.refused;
+        if (plan.family == GEMM_TILE) ok = ok && q[1] == plan.BM && q[2] == plan.BN && q[3] == (plan.deep ? 1 : 0);
+        else ok = ok && q[1] == (plan.family == GEMM_PP256 ? 256 : plan.family == GEMM_PP128 ? 128 : 32) && q[2] == 320 && q[3] == 0;
         if (!r.refused) {
             ok = ok && (int)plan.family == r.family;
             if (r.family == GEMM_TILE)
@@ -496,6 +503,29 @@ int main(int argc, char** argv) {
         }
         vsx_set_option("tile_tune", 0);
         vsx_set_option("xcd_walk", 1);
+    }
+    if (only < 0 || only == nplain + 14) {
+        // forced split counts that would leave the last K slice without a slab (5 slabs in 4 slices of ceil = 2: 2 + 2 + 1 + 0; the
+        // automatic planner never asks for one): plan_splitk takes slices away until every slice has one.  An empty slice's
+        // workgroups multiplied whatever the LDS ring held.
+        struct E { const char* name; long K, tune; int splits; };
+        const E cases[] = {{"split-K 100x320x320, 4 slices forced over 5 slabs -> 3", 320, (4 << 8), 3},
+                           {"split-K 100x320x256, 3 slices forced over 4 slabs -> 2", 256, (3 << 8), 2}};
+        for (const E& e : cases) {
+            Plain c = {e.name, 100, 320, e.K, true, false, false, false, false, 0, 0, 0, true};
+            vsx_set_option("tile_tune", e.tune);
+            rng_state = 31u;
+            run_plain(c, true);
+            vsx_gemm_desc d{};
+            d.M = c.M; d.N = c.N; d.K = c.K; d.batch0 = d.batch1 = 1; d.lda = d.ldb = c.K; d.ldc = c.N; d.alpha = 1.0; d.pad_lo = d.pad_hi = -1;
+            d.A = d.B = d.C = d.workspace = reinterpret_cast<void*>(0x10000000);
+            d.workspace_bytes = vsx_gemm_workspace(&d);
+            int64_t q[8];
+            const bool ok = vsx_gemm_plan(&d, q) == VSX_OK && q[4] == e.splits && (q[4] - 1) * q[5] < (c.K + 63) / 64;
+            printf("%-58s %s (%ld slices of %ld slabs)\n", "  ... no slice without a slab", ok ? "ok" : "FAIL", (long)q[4], (long)q[5]);
+            n_bad += ok ? 0 : 1;
+        }
+        vsx_set_option("tile_tune", 0);
     }
     if (only < 0 || only == nplain + 9) {
         // residual prefetch of the tile kernels BEHIND the last slab (gemm.hip, RES_LATE): ten slabs, every forced tile / ring

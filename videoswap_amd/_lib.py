@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 15
+VSX_ABI_VERSION = 16
 VSX_E_UNSUPPORTED = -2
 
 
@@ -61,6 +61,7 @@ PROTOTYPES = {
     'vsx_gemm_f16': (c_int, [POINTER(GemmDesc), c_void_p]),
     'vsx_gemm_check': (c_int, [POINTER(GemmDesc)]),
     'vsx_gemm_workspace': (c_int64, [POINTER(GemmDesc)]),
+    'vsx_gemm_plan': (c_int, [POINTER(GemmDesc), POINTER(c_int64)]),
     'vsx_gemm_rowstats_parts': (c_int64, [POINTER(GemmDesc)]),
     # Winograd F(2x2, 3x3) form of the stride-1 3x3 convolutions (csrc/winograd.hip)
     'vsx_conv3x3_winograd_workspace': (c_int64, [POINTER(GemmDesc)]),

@@ -892,7 +892,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
 // no split) for a problem whose wide tiles would number `tiles`.
 inline int plan_splitk(const vsx_gemm_desc* d, long tiles, bool eligible) {
     const long nk = (d->K + BK - 1) / BK;
-    if (eligible && tune_splits() > 0) return tune_splits() <= nk ? tune_splits() : (int)nk;
+    if (eligible && tune_splits() > 0) {
+        // a forced count (the planner below never makes one) must not leave the last slice without a slab: its workgroups would
+        // multiply whatever the LDS ring holds.  Slices are ceil(nk / s) slabs long; fewer slices until the last one has a slab.
+        int s = tune_splits() <= nk ? tune_splits() : (int)nk;
+        while (s > 1 && (long)(s - 1) * ((nk + s - 1) / s) >= nk) --s;
+        return s;
+    }
     if (!eligible || tiles >= 160) return 1;
     int s = (int)((256 + tiles - 1) / tiles);
     if (s > 8) s = 8;
@@ -1342,6 +1348,28 @@ extern "C" int64_t vsx_gemm_workspace(const vsx_gemm_desc* d) {
     GemmParams p;
     if (!d || d->M <= 0 || fill_params(d, p) != VSX_OK) return 0;
     return plan_gemm(*d, p, true).workspace_bytes;
+}
+
+// What vsx_gemm_f16(d, ...) would launch under the current option values: check_and_plan's answer as eight numbers (vsx.h), and
+// its status.  No HIP call; nothing d points at is read.
+extern "C" int vsx_gemm_plan(const vsx_gemm_desc* d, int64_t out[8]) {
+    if (out == nullptr) return vsx_fail(VSX_E_BADSHAPE, "gemm: vsx_gemm_plan needs eight int64 to write to");
+    GemmParams p;
+    GemmPlan plan{};
+    plan.family = (GemmFamily)-1;
+    const int rc = check_and_plan(d, p, plan);      // (the plan is made before its refusals are reported)
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = (int64_t)(int)plan.family;
+    if ((int)plan.family < 0) return rc;
+    const bool tile = plan.family == GEMM_TILE;
+    out[1] = tile ? plan.BM : plan.family == GEMM_PP256 ? 256 : plan.family == GEMM_PP128 ? 128 : 32;
+    out[2] = tile ? plan.BN : 320;
+    out[3] = tile && plan.deep ? 1 : 0;
+    out[4] = plan.splits;
+    out[5] = plan.splits > 1 ? plan.nk_per : 0;
+    out[6] = plan.stat_parts;
+    out[7] = (int64_t)plan.refused;
+    return rc;
 }
 
 // The status vsx_gemm_f16(d, ...) would return under the current option values, without launching anything (the caller asks
