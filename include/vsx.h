@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VSX_ABI_VERSION 16
+#define VSX_ABI_VERSION 17
 
 #define VSX_OK 0
 #define VSX_E_BADSHAPE (-1)
@@ -650,6 +650,73 @@ int vsx_hash_grid_bwd_f32(const float* x, int64_t N, int64_t input_dim, const fl
                           int64_t table_floats, int64_t n_levels, int64_t n_features, int64_t log2_hashmap_size,
                           int64_t base_resolution, double per_level_scale, float* grad_table, float* grad_x,
                           vsx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K18 (ABI 17, additive): the data gather and the losses of a layered-neural-atlas training step (train_atlas.py:127-253,
+ * videoswap/atlas/loss_utils.py; csrc/atlas_loss.hip).  fp32 throughout; every pointer 4-byte aligned (idx 8).
+ *
+ * vsx_atlas_batch_f32 (K18a, one launch and the clearing of `counts`): idx [N] int64, flat pixel indices in the (frame, row,
+ *   column) order of get_tuples: f = idx / (H W), i = idx % (H W) / W, j = idx % W.  The arrays of load_input_data in the
+ *   reference's layouts: video, video_dx, video_dy [H, W, 3, T]; mask [H, W, T]; flow, flow_rev [H, W, 2, T, 1]; flow_mask,
+ *   flow_rev_mask [H, W, T, 1], relevant where non-zero.  d = derivative_amount, D = global_derivative_amount.
+ *   rows [B][N][3], B = 9 with_global, else 7 (blocks 5 and 6 absent, the flow matches at 5 and 6):
+ *     0 (x, y, t)   1 (x + 1, y, t)   2 (x, y + 1, t)   3 (x, y - d, t)   4 (x - d, y, t)   5 (x, y - D, t)   6 (x - D, y, t)
+ *     7 (x + fx, y + fy, t + 1), the forward flow match      8 (x + rx, y + ry, t - 1), the backward flow match
+ *   each coordinate as torch computes it on the CPU in the reference: (float)c / (float)(larger_dim / 2.0) - 1, larger_dim =
+ *   max(H, W), the time (float)f / (float)(T / 2.0) - 1, the flow match ((float)j + fx) first; IEEE divisions, no reciprocal:
+ *   every output is bit-equal to the torch statement.  Offsets may leave the image (x + 1 = W, x - D < 0, t + 1 = T): these
+ *   are coordinates only, every table read uses the sampled pixel.  Blocks 7 and 8 hold all N rows, relevant or not.
+ *   rgb, rgb_dx, rgb_dy [N, 3]; alpha_gt [N]; m_fwd, m_bwd [N] in {0, 1}; counts int32 [2] = the sums of m_fwd and of m_bwd
+ *   (integer atomic adds: exact, order-independent).  N == 0: counts are cleared, nothing is launched.
+ *   An idx outside 0 .. T H W - 1 reads nothing: its rows, colours and alpha_gt are NaN, its m_fwd and m_bwd 0 (the Python
+ *   binding refuses such a batch on the host before it copies it).
+ *   Refused, nothing written: flow_levels != 1 (VSX_E_UNSUPPORTED); a null or misaligned pointer, H, W, T, d or D < 1
+ *   (VSX_E_BADSHAPE).
+ *
+ * vsx_atlas_losses_f32 (K18b, two launches whatever N is): uv_fg, uv_bg [B N, 2], the mapping networks' outputs on `rows`;
+ *   alpha_raw [5 N], F_Alpha's tanh output on the blocks 0, 1, 2, 7, 8; rgb_atlas [6 N, 3], F_Atlas's tanh output on
+ *   uv_fg * 0.5 + 0.5 of the blocks 0, 1, 2, then on uv_bg * 0.5 - 0.5 of the same; K18a's outputs; cfg below ->
+ *   losses [14]: 0 gradient, 1 rgb, 2 alpha, 3 sparsity, 4 rigidity fg, 5 rigidity bg, 6 global rigidity fg, 7 global rigidity
+ *     bg, 8 flow fg, 9 flow bg, 10 flow_alpha, 11 total, 12 alpha_mean_fg, 13 alpha_mean_bg.  The definitions are the
+ *     reference's (train_atlas.py:152-162, 180-196; loss_utils.py:5-48, 52-112, 132-153 with use_alpha, 212-233); a term that
+ *     is switched off (alpha without with_alpha_loss, global rigidity without with_global_rigidity) is 0 and not in the total.
+ *   g_uv_fg, g_uv_bg, g_alpha_raw, g_rgb_atlas: the gradient of losses[11] with respect to the four inputs, in their shapes.
+ *     alpha is NOT detached in the flow losses; rgb_output of block 0 enters the gradient loss; uv of block 0 enters both
+ *     rigidity losses and both flow losses; uv of the blocks 1 and 2 reaches the losses through F_Atlas only (zero here).
+ *   A flow mean is sum(m term) / sum(m) over all N rows with the 0/1 weights m; a row with m = 0 contributes nothing and gets
+ *     a zero gradient whatever the networks gave for it (a select, not a product).  DEVIATION: with no relevant row the term
+ *     is 0 with a zero gradient (NaN in the reference).  alpha_mean_fg / _bg are sum / count over alpha > 0.5 / < 0.5 (strict),
+ *     NaN on an empty set as in the reference; log values, no gradient.  The gradient of a norm at the zero vector and of |x|
+ *     at 0 is 0 (torch's conventions); so is the gradient of the sqrt of an all-zero JtJ (NaN in torch).
+ *   Summation: launch 1 takes one row per thread and writes its entries of the four gradients (one writer per entry); the 18
+ *     per-row sums (csrc/atlas_loss.hip AL_TERMS) are added over a wave by xor-shuffles (32, 16, .. 1), over the four waves of
+ *     a 256-row workgroup in wave order, and stored per workgroup in scratch; launch 2 adds the workgroups in index order and
+ *     divides.  No atomics: two calls give the same bits.  scratch: vsx_atlas_losses_workspace(N) floats, overwritten.
+ *   N == 0: only launch 2 runs; the means over N are 0 / 0 = NaN as in torch, no gradient is written.
+ *   The reference's `assert not isnan / isinf` on the Jacobians has no equivalent (it would need a host sync per step): a
+ *   non-finite value shows in losses[11].
+ *   Refused, nothing written: a null or misaligned pointer, larger_dim or a derivative amount < 1, uv_mapping_scale <= 0
+ *   (VSX_E_BADSHAPE); a short scratch (VSX_E_WORKSPACE).
+ * All fields are 8 bytes so the struct has no padding on any ABI.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct vsx_atlas_loss_cfg {
+    double gradient_loss_weight, rgb_loss_weight, alpha_loss_weight, sparsity_loss_weight, rigidity_loss_weight;
+    double global_rigidity_fg_loss_weight, global_rigidity_bg_loss_weight, flow_loss_weight, alpha_flow_loss_weight;
+    double uv_mapping_scale;
+    int64_t larger_dim, derivative_amount, global_derivative_amount;
+    int64_t with_alpha_loss, with_global_rigidity;
+} vsx_atlas_loss_cfg;
+int vsx_atlas_batch_f32(const int64_t* idx, int64_t N, int64_t H, int64_t W, int64_t T, int64_t flow_levels, const float* video,
+                        const float* video_dx, const float* video_dy, const float* mask, const float* flow, const float* flow_rev,
+                        const float* flow_mask, const float* flow_rev_mask, int64_t d, int64_t D, int64_t with_global,
+                        float* rows, float* rgb, float* rgb_dx, float* rgb_dy, float* alpha_gt, float* m_fwd, float* m_bwd,
+                        int32_t* counts, vsx_stream_t stream);
+int64_t vsx_atlas_losses_workspace(int64_t N);
+int vsx_atlas_losses_f32(const float* uv_fg, const float* uv_bg, const float* alpha_raw, const float* rgb_atlas, int64_t N,
+                         const float* rgb, const float* rgb_dx, const float* rgb_dy, const float* alpha_gt, const float* m_fwd,
+                         const float* m_bwd, const int32_t* counts, const vsx_atlas_loss_cfg* cfg, float* losses, float* g_uv_fg,
+                         float* g_uv_bg, float* g_alpha_raw, float* g_rgb_atlas, float* scratch, int64_t scratch_floats,
+                         vsx_stream_t stream);
 
 #ifdef __cplusplus
 }

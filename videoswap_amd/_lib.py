@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 VARIANT = os.environ.get('VSX_LIB_VARIANT') or None
 LIB_PATH = os.path.join(_HERE, 'lib', 'libvsx.so' if not VARIANT else f'libvsx_{VARIANT}.so')
 
-VSX_ABI_VERSION = 16
+VSX_ABI_VERSION = 17
 VSX_E_UNSUPPORTED = -2
 
 
@@ -49,6 +49,15 @@ class GemmDesc(Structure):
         ('rowscale', c_void_p), ('colvec', c_void_p),
         ('rowstats', c_void_p), ('rowstats_parts', c_int64),
     ]
+
+
+class AtlasLossCfg(Structure):
+    """Mirror of ``struct vsx_atlas_loss_cfg`` (every field is 8 bytes)"""
+    _fields_ = [(k, c_double) for k in (
+        'gradient_loss_weight', 'rgb_loss_weight', 'alpha_loss_weight', 'sparsity_loss_weight', 'rigidity_loss_weight',
+        'global_rigidity_fg_loss_weight', 'global_rigidity_bg_loss_weight', 'flow_loss_weight', 'alpha_flow_loss_weight',
+        'uv_mapping_scale')] + [(k, c_int64) for k in (
+            'larger_dim', 'derivative_amount', 'global_derivative_amount', 'with_alpha_loss', 'with_global_rigidity')]
 
 
 # name -> (restype, argtypes); every symbol of include/vsx.h
@@ -154,6 +163,11 @@ PROTOTYPES = {
                              + [c_void_p, c_int64] * 4 + [c_void_p] * 3),
     'vsx_hash_grid_bwd_f32': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p] + [c_int64] * 5 + [c_double]
                               + [c_void_p] * 3),
+    # the batch gather and the fused losses of an atlas training step (csrc/atlas_loss.hip, K18)
+    'vsx_atlas_batch_f32': (c_int, [c_void_p] + [c_int64] * 5 + [c_void_p] * 8 + [c_int64] * 3 + [c_void_p] * 9),
+    'vsx_atlas_losses_workspace': (c_int64, [c_int64]),
+    'vsx_atlas_losses_f32': (c_int, [c_void_p] * 4 + [c_int64] + [c_void_p] * 7 + [POINTER(AtlasLossCfg)] + [c_void_p] * 6
+                             + [c_int64, c_void_p]),
 }
 
 # entry points that only a development variant exports (typed when present); none at the moment

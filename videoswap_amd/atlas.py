@@ -569,5 +569,5 @@ def checkerboard_videos(models, res_x, res_y, number_of_frames, area_fg, area_bg
     return dict(checkerboard_fg=cfg, checkerboard_bg=cbg, texture_fg=texs[0], texture_bg=texs[1], launches=out['launches'] + 2)
 
 
-from .atlas_fit import (fit_inverse_mapping, fit_reconstruction, load_mask_frames, pretrain_mapping,  # noqa: E402,F401
-                        reconstruction_losses)                                                   # (the fitting half)
+from .atlas_fit import (fit_atlas, fit_inverse_mapping, fit_reconstruction, load_mask_frames, pretrain_mapping,  # noqa: E402,F401
+                        reconstruction_losses, training_losses)                                                  # (the fitting half)

@@ -31,7 +31,7 @@ VARIANTS = {}
 # variant name -> additional sources (relative to csrc/)
 VARIANT_EXTRA = {}
 SOURCES = ['api.cpp', 'comm.cpp', 'options.cpp', 'prof.cpp', 'gemm.hip', 'gemm_pp.hip', 'norm.hip', 'attention.hip', 'attention_bwd.hip', 'elementwise.hip',
-           'train.hip', 'dift.hip', 'atlas.hip', 'atlas_bwd.hip', 'atlas_edit.hip', 'winograd.hip']
+           'train.hip', 'dift.hip', 'atlas.hip', 'atlas_bwd.hip', 'atlas_edit.hip', 'atlas_loss.hip', 'winograd.hip']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-x', 'hip',
          '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-Wall', '-Wno-unused-function', '-Wno-division-by-zero',
@@ -107,7 +107,7 @@ LLVM_BIN = os.environ.get('VSX_LLVM_BIN', '/opt/rocm/lib/llvm/bin')
 # VMEM operation in that queue, so these must compile without spills and without a private segment (gemm_pp.hip:33-37)
 # (matched on the MANGLED names: gemm_kernelILi256E... = gemm_kernel<256, ...>)
 NO_SCRATCH = ('gemm_pp_kernel', 'gemm_ws320_kernel', 'flash_attn_kernel', 'gemm_kernelILi256E', 'coord_mlp_kernel', 'wino_input_kernel',
-              'wino_output_kernel')
+              'wino_output_kernel', 'atlas_batch_kernel', 'atlas_losses_rows_kernel', 'atlas_losses_finish_kernel')
 
 
 def parse_kernel_notes(text):

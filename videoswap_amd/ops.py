@@ -1133,6 +1133,100 @@ def atlas_edit(uv_fg, uv_bg, alpha, tex_fg, box_fg, tex_bg, box_bg, base_fg=None
     return edit, fg, bg, relevant
 
 
+ATLAS_DATA_KEYS = ('video_frames', 'video_frames_dx', 'video_frames_dy', 'mask_frames', 'optical_flows', 'optical_flows_reverse',
+                   'optical_flows_mask', 'optical_flows_reverse_mask')
+ATLAS_LOSSES = ('gradient_loss', 'rgb_loss', 'alpha_loss', 'sparsity_loss', 'rigidity_loss_fg', 'rigidity_loss_bg',
+                'global_rigidity_loss_fg', 'global_rigidity_loss_bg', 'flow_loss_fg', 'flow_loss_bg', 'flow_alpha_loss', 'total_loss',
+                'alpha_mean_fg', 'alpha_mean_bg')           # the order of `losses` (vsx.h K18)
+
+
+def atlas_batch(idx, data, derivative_amount, global_derivative_amount, with_global_rigidity=True):
+    """The data gather of an atlas training step in one launch (include/vsx.h K18a): idx int64 [N] or [N, 1], flat pixel
+    indices in the (frame, row, column) order of get_tuples, on the CPU (checked against T H W there, then copied: 8 N bytes)
+    or on the GPU (unchecked: the kernel gives such a row NaNs); `data`: load_input_data's data_dict on the GPU, fp32, in
+    the reference's layouts -> dict(rows [B, N, 3] with B = 9 or 7, rgb / rgb_dx / rgb_dy [N, 3], alpha_gt / m_fwd / m_bwd
+    [N], counts int32 [2], larger_dim, with_global_rigidity).  Every float is bit-equal to the reference's torch statement
+    on the CPU.  Another flow level count than 1 raises NotImplementedError, bad buffers VsxError."""
+    for k in ATLAS_DATA_KEYS:
+        _chk(data[k], k, torch.float32)
+    video, flows = data['video_frames'], data['optical_flows']
+    if video.dim() != 4 or video.shape[2] != 3:
+        raise _lib.VsxError(f'atlas_batch: video_frames must be [H, W, 3, T], got {tuple(video.shape)}')
+    H, W, _, T = video.shape
+    if flows.dim() != 5 or tuple(flows.shape[:4]) != (H, W, 2, T):
+        raise _lib.VsxError(f'atlas_batch: optical_flows must be [{H}, {W}, 2, {T}, levels], got {tuple(flows.shape)}')
+    levels = flows.shape[4]
+    want = {'video_frames_dx': (H, W, 3, T), 'video_frames_dy': (H, W, 3, T), 'mask_frames': (H, W, T),
+            'optical_flows_reverse': (H, W, 2, T, levels), 'optical_flows_mask': (H, W, T, levels),
+            'optical_flows_reverse_mask': (H, W, T, levels)}
+    for k, shape in want.items():
+        if tuple(data[k].shape) != shape:
+            raise _lib.VsxError(f'atlas_batch: {k} must be {list(shape)}, got {tuple(data[k].shape)}')
+    idx = idx.reshape(-1)
+    if idx.dtype != torch.int64:
+        raise _lib.VsxError(f'atlas_batch: idx must be int64, got {idx.dtype}')
+    N, dev = idx.numel(), video.device
+    if not idx.is_cuda:
+        if N and (int(idx.min()) < 0 or int(idx.max()) >= T * H * W):
+            raise _lib.VsxError(f'atlas_batch: idx outside 0 .. {T * H * W - 1} (T H W = {T} x {H} x {W})')
+        idx = idx.to(dev)
+    idx = idx.contiguous()
+    B = 9 if with_global_rigidity else 7
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(rows=torch.empty(B, N, 3, **f32), rgb=torch.empty(N, 3, **f32), rgb_dx=torch.empty(N, 3, **f32),
+               rgb_dy=torch.empty(N, 3, **f32), alpha_gt=torch.empty(N, **f32), m_fwd=torch.empty(N, **f32),
+               m_bwd=torch.empty(N, **f32), counts=torch.empty(2, dtype=torch.int32, device=dev))
+    rc = _lib.load().vsx_atlas_batch_f32(
+        _p(idx), N, H, W, T, levels, *(_p(data[k]) for k in ATLAS_DATA_KEYS), int(derivative_amount), int(global_derivative_amount),
+        int(bool(with_global_rigidity)), *(_p(out[k]) for k in ('rows', 'rgb', 'rgb_dx', 'rgb_dy', 'alpha_gt', 'm_fwd', 'm_bwd', 'counts')),
+        _stream())
+    _check_supported(rc, 'vsx_atlas_batch_f32')
+    out.update(larger_dim=max(H, W), with_global_rigidity=bool(with_global_rigidity))
+    return out
+
+
+def atlas_losses(uv_fg, uv_bg, alpha_raw, rgb_atlas, batch, cfg):
+    """Every loss of an atlas training step and the gradient of total_loss with respect to the four network outputs, in
+    two launches (include/vsx.h K18b): uv_fg, uv_bg fp32 [B N, 2] (the mapping networks on batch['rows']), alpha_raw [5 N]
+    or [5 N, 1] (F_Alpha's tanh output on the blocks 0, 1, 2 and the two flow matches), rgb_atlas [6 N, 3] (F_Atlas's tanh
+    output on the foreground, then the background queries of the blocks 0, 1, 2); `batch` from `atlas_batch`; cfg: the nine
+    weights, uv_mapping_scale, derivative_amount, global_derivative_amount and with_alpha_loss by the field names of
+    vsx_atlas_loss_cfg -> (losses [14] in the order ATLAS_LOSSES, g_uv_fg, g_uv_bg, g_alpha_raw, g_rgb_atlas).  No atomics:
+    two calls give the same bits."""
+    N = batch['rgb'].shape[0]
+    B = batch['rows'].shape[0]
+    for t, name, shape in ((uv_fg, 'uv_fg', (B * N, 2)), (uv_bg, 'uv_bg', (B * N, 2)), (rgb_atlas, 'rgb_atlas', (6 * N, 3))):
+        _chk(t, name, torch.float32)
+        if tuple(t.shape) != shape:
+            raise _lib.VsxError(f'atlas_losses: {name} must be {list(shape)}, got {tuple(t.shape)}')
+    _chk(alpha_raw, 'alpha_raw', torch.float32)
+    if alpha_raw.numel() != 5 * N or alpha_raw.dim() > 2:
+        raise _lib.VsxError(f'atlas_losses: alpha_raw must hold {5 * N} values, got {tuple(alpha_raw.shape)}')
+    for k in ('rgb', 'rgb_dx', 'rgb_dy', 'alpha_gt', 'm_fwd', 'm_bwd'):
+        _chk(batch[k], k, torch.float32)
+    _chk(batch['counts'], 'counts', torch.int32)
+    c = _lib.AtlasLossCfg()
+    for k, _ in _lib.AtlasLossCfg._fields_:
+        if k == 'larger_dim':
+            c.larger_dim = int(batch['larger_dim'])
+        elif k == 'with_global_rigidity':
+            c.with_global_rigidity = int(B == 9)
+        elif k in ('derivative_amount', 'global_derivative_amount', 'with_alpha_loss'):
+            setattr(c, k, int(cfg[k]))
+        else:
+            setattr(c, k, float(cfg[k]))
+    lib = _lib.load()
+    dev = uv_fg.device
+    losses = torch.empty(14, dtype=torch.float32, device=dev)
+    grads = [torch.empty_like(t) for t in (uv_fg, uv_bg, alpha_raw, rgb_atlas)]
+    scratch = torch.empty(lib.vsx_atlas_losses_workspace(N), dtype=torch.float32, device=dev)
+    rc = lib.vsx_atlas_losses_f32(_p(uv_fg), _p(uv_bg), _p(alpha_raw), _p(rgb_atlas), N,
+                                  *(_p(batch[k]) for k in ('rgb', 'rgb_dx', 'rgb_dy', 'alpha_gt', 'm_fwd', 'm_bwd', 'counts')),
+                                  ctypes.byref(c), _p(losses), *(_p(g) for g in grads), _p(scratch), scratch.numel(), _stream())
+    _check_supported(rc, 'vsx_atlas_losses_f32')
+    return (losses, *grads)
+
+
 def set_option(name, value):
     """Process-wide tuning / test switch of libvsx (the table in csrc/options.cpp).  The library holds the only copy: the
     host-side choices that depend on an option (`_conv_form`) ask the library, which reads it there."""
@@ -1367,7 +1461,8 @@ _PLAIN = ('gemm', 'set_option', 'get_option', 'prof_pause', 'prof_enable', 'prof
           'group_norm_bwd', 'layer_norm_bwd', 'softmax_bwd', 'sum_pool2x2', 'adapter_gather', 'attention_lse',
           'attention_bwd', 'attention_bwd_supported', 'dift_sample_points', 'dift_cosine_map', 'coord_mlp', 'hash_grid',
           'hash_mlp', 'atlas_edit', 'coord_mlp_train_workspace', 'coord_mlp_train_forward', 'coord_mlp_backward',
-          'hash_grid_backward', 'hash_mlp_train_workspace', 'hash_mlp_train_forward', 'hash_mlp_backward')
+          'hash_grid_backward', 'hash_mlp_train_workspace', 'hash_mlp_train_forward', 'hash_mlp_backward', 'atlas_batch',
+          'atlas_losses')
 
 
 def _publish(name):

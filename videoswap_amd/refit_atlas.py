@@ -6,8 +6,8 @@ they differ, as render_atlas reads them) and the foreground masks (`--mask_dir`,
 losses of train_atlas.py) are run on the networks named by `--train`, and `--save_path` receives a
 checkpoint that the other tools load: every entry of the input checkpoint, the trained networks replaced.  By default only
 F_Atlas is trained and the mapping networks stay frozen, so the parametrisation stays valid for point propagation and for
-textures edited earlier.  The gradient, rigidity and flow losses of train_atlas.py are not implemented: with the mapping
-networks in `--train` nothing keeps the mappings rigid.
+textures edited earlier.  The gradient, rigidity and flow losses of train_atlas.py are not used here
+(videoswap_amd.train_atlas runs them): with the mapping networks in `--train` nothing keeps the mappings rigid.
 """
 import argparse
 import os
