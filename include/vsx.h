@@ -171,7 +171,9 @@ int64_t vsx_gemm_workspace(const vsx_gemm_desc* d);
  *   U: the transformed weights G g G^T, fp16 [16][N][C1+C2] (xi = 4 a + b outermost), made by the caller from B =
  *      [N, 3, 3, C1+C2] (videoswap_amd.ops.winograd_weights); d->B is not read.
  *   workspace: caller-allocated, 16-byte aligned, vsx_conv3x3_winograd_workspace(d) bytes (V, then Mt); that function
- *      returns 0 for a description this form does not take.
+ *      returns 0 for a description this form does not take.  V is fp16 [16][M/4][C1+C2] at the start, Mt fp16 [16][M/4][N]
+ *      right behind it (xi = 4 a + b outermost in both; tile = (image, row / 2, column / 2), row-major).  The call writes
+ *      every element of both and clears nothing: both can be read back after it (tests/winograd_case.py does).
  *   Supported: a_mode 1, ks 3, stride 1, upsample 0, symmetric padding 1 (pad_lo = pad_hi = -1 or 1), H and W even, no
  *      batch, C1 / C2 / N multiples of 8 (two sources: C1, C2 multiples of 64), ldc / ldr multiples of 8, alpha 1,
  *      epilogue = bias / rowvec / residual.  Anything else: VSX_E_UNSUPPORTED; the library never falls back by itself.

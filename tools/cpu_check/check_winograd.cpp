@@ -10,6 +10,9 @@
 
 #include <stdarg.h>
 #include <stdlib.h>
+#include <string.h>
+
+#include <utility>
 
 // ---- pieces of the HIP runtime / gfx950 builtins only gemm.hip needs (as in check_gemm_api.cpp) ----
 struct uint2 { unsigned x, y; };
@@ -71,6 +74,9 @@ CPUHIP_DEFINE_LDS
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
+
+#include <utility>
 
 #include "common.h"
 
@@ -141,7 +147,8 @@ static const double BT[4][4] = {{1, 0, -1, 0}, {0, 1, 1, 0}, {0, -1, 1, 0}, {0, 
 static const double AT[2][4] = {{1, 1, 1, 0}, {0, 1, -1, -1}};
 static const double G[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
 
-struct Geo { int nimg, H, W, C1, C2, N; bool bias, rowvec, res; };
+// rpv: rows_per_vec (0: two images); cpad, rpad: ldc = N + cpad, ldr = N + rpad
+struct Geo { int nimg, H, W, C1, C2, N; bool bias, rowvec, res; long rpv = 0; int cpad = 0, rpad = 0; };
 
 static double pixel(const HBuf& a, const HBuf& a2, const Geo& g, int img, int y, int x, int c) {
     if (y < 0 || y >= g.H || x < 0 || x >= g.W) return 0.0;
@@ -178,14 +185,33 @@ static void run_input(const Geo& g) {
     verdict(name, 0, num, den, 4e-4);                    // one rounding to fp16: 2^-11 / sqrt 3 = 2.8e-4 at the worst
 }
 
-// rows_per_vec spans two images
-static long rpv(const Geo& g) { return 2L * g.H * g.W; }
+// rows_per_vec: what the geometry names, else a vector spans two images
+static long rpv(const Geo& g) { return g.rpv ? g.rpv : 2L * g.H * g.W; }
+
+// C with ldc = N + cpad: exactly (M - 1) ldc + N halves (a store behind the last row's N columns is a sanitizer report), the pad
+// columns of the other rows hold a sentinel that must survive the call
+static const float PAD_SENTINEL = 777.f;
+static size_t padded(long M, int N, int pad) { return (size_t)(M - 1) * (N + pad) + N; }
+static void fill_pads(HBuf& y, long M, int N, int pad) {
+    for (long r = 0; r + 1 < M; ++r)
+        for (int c = N; c < N + pad; ++c) y.p[(size_t)r * (N + pad) + c] = (half_t)PAD_SENTINEL;
+}
+static bool pads_intact(const HBuf& y, long M, int N, int pad) {
+    for (long r = 0; r + 1 < M; ++r)
+        for (int c = N; c < N + pad; ++c)
+            if (y[(size_t)r * (N + pad) + c] != (double)PAD_SENTINEL) return false;
+    return true;
+}
+static void tag(char* name, size_t n, const Geo& g) {
+    const size_t at = strlen(name);
+    if (g.rpv || g.cpad || g.rpad) snprintf(name + at, n - at, " rpv %ld ldc N+%d ldr N+%d", rpv(g), g.cpad, g.rpad);
+}
 
 static double epilogue(const Geo& g, const HBuf& bias, const HBuf& rowvec, const HBuf& res, long row, int n) {
     double e = 0;
     if (g.bias) e += bias[n];
     if (g.rowvec) e += rowvec[(size_t)(row / rpv(g)) * g.N + n];
-    if (g.res) e += res[(size_t)row * g.N + n];
+    if (g.res) e += res[(size_t)row * (g.N + g.rpad) + n];
     return e;
 }
 
@@ -193,12 +219,13 @@ static double epilogue(const Geo& g, const HBuf& bias, const HBuf& rowvec, const
 static void run_output(const Geo& g) {
     const int th = g.H / 2, tw = g.W / 2;
     const long tiles = (long)g.nimg * th * tw, M = 4 * tiles;
-    HBuf mt((size_t)16 * tiles * g.N, 1.f), y((size_t)M * g.N), bias(g.N, 0.5f), rowvec((size_t)((M + rpv(g) - 1) / rpv(g)) * g.N, 0.5f);
-    HBuf res((size_t)M * g.N, 1.f);
+    HBuf mt((size_t)16 * tiles * g.N, 1.f), y(padded(M, g.N, g.cpad)), bias(g.N, 0.5f), rowvec((size_t)((M + rpv(g) - 1) / rpv(g)) * g.N, 0.5f);
+    HBuf res(padded(M, g.N, g.rpad), 1.f);
+    fill_pads(y, M, g.N, g.cpad);
     WinoOut p;
     p.Mt = mt.p; p.Y = y.p; p.bias = g.bias ? bias.p : nullptr; p.rowvec = g.rowvec ? rowvec.p : nullptr;
     p.residual = g.res ? res.p : nullptr;
-    p.rows_per_vec = rpv(g); p.ldc = g.N; p.ldr = g.N;
+    p.rows_per_vec = rpv(g); p.ldc = g.N + g.cpad; p.ldr = g.N + g.rpad;
     p.H = g.H; p.W = g.W; p.N = g.N; p.th = th; p.tw = tw; p.tiles = tiles;
     const long n = tiles * (g.N / 8);
     hipLaunchKernelGGL(wino_output_kernel, dim3((unsigned)((n + WG_THREADS - 1) / WG_THREADS)), dim3(WG_THREADS), 0, nullptr, p);
@@ -213,7 +240,7 @@ static void run_output(const Geo& g) {
                         for (int xb = 0; xb < 4; ++xb) want += AT[pi][xa] * mt[((size_t)(4 * xa + xb) * tiles + t) * g.N + c] * AT[pj][xb];
                     const long row = ((long)img * g.H + 2 * ti + pi) * g.W + 2 * tj + pj;
                     want += epilogue(g, bias, rowvec, res, row, c);
-                    const double d = y[(size_t)row * g.N + c] - want;
+                    const double d = y[(size_t)row * (g.N + g.cpad) + c] - want;
                     num += d * d;
                     den += want * want;
                 }
@@ -221,7 +248,8 @@ static void run_output(const Geo& g) {
     char name[128];
     snprintf(name, sizeof(name), "output transform %dx%dx%d N=%d%s%s%s", g.nimg, g.H, g.W, g.N, g.bias ? " bias" : "", g.rowvec ? " rowvec" : "",
              g.res ? " residual" : "");
-    verdict(name, 0, num, den, 4e-4);
+    tag(name, sizeof(name), g);
+    verdict(name, pads_intact(y, M, g.N, g.cpad) ? 0 : -1, num, den, 4e-4);
 }
 
 static vsx_gemm_desc conv_desc(const Geo& g) {
@@ -229,7 +257,7 @@ static vsx_gemm_desc conv_desc(const Geo& g) {
     d.M = (int64_t)g.nimg * g.H * g.W; d.N = g.N; d.K = 9 * (g.C1 + g.C2);
     d.batch0 = d.batch1 = 1;
     d.a_mode = 1; d.H = g.H; d.W = g.W; d.C1 = g.C1; d.C2 = g.C2; d.ks = 3; d.stride = 1;
-    d.ldb = d.K; d.ldc = g.N; d.ldr = g.N; d.alpha = 1.0;
+    d.ldb = d.K; d.ldc = g.N + g.cpad; d.ldr = g.N + g.rpad; d.alpha = 1.0;
     d.pad_lo = d.pad_hi = -1;
     return d;
 }
@@ -239,8 +267,9 @@ static void run_entry(const Geo& g) {
     const int C = g.C1 + g.C2;
     const long M = (long)g.nimg * g.H * g.W, tiles = M / 4;
     const float wscale = 1.0f / sqrtf(9.0f * C);
-    HBuf a((size_t)M * g.C1, 1.f), a2((size_t)M * g.C2, 1.f), w((size_t)g.N * 9 * C, wscale), u((size_t)16 * g.N * C), y((size_t)M * g.N);
-    HBuf bias(g.N, 0.5f), rowvec((size_t)((M + rpv(g) - 1) / rpv(g)) * g.N, 0.5f), res((size_t)M * g.N, 1.f);
+    HBuf a((size_t)M * g.C1, 1.f), a2((size_t)M * g.C2, 1.f), w((size_t)g.N * 9 * C, wscale), u((size_t)16 * g.N * C), y(padded(M, g.N, g.cpad));
+    HBuf bias(g.N, 0.5f), rowvec((size_t)((M + rpv(g) - 1) / rpv(g)) * g.N, 0.5f), res(padded(M, g.N, g.rpad), 1.f);
+    fill_pads(y, M, g.N, g.cpad);
     for (int n = 0; n < g.N; ++n)                        // U = G g G^T, rounded once (videoswap_amd.ops.winograd_weights)
         for (int c = 0; c < C; ++c)
             for (int xa = 0; xa < 4; ++xa)
@@ -258,7 +287,8 @@ static void run_entry(const Geo& g) {
     const int64_t need = vsx_conv3x3_winograd_workspace(&d);
     bool ok = need == 16 * tiles * (C + g.N) * 2;
     HBuf ws((size_t)need / 2);
-    const int rc = ok ? vsx_conv3x3_winograd_f16(&d, u.p, ws.p, need, nullptr) : -100;
+    int rc = ok ? vsx_conv3x3_winograd_f16(&d, u.p, ws.p, need, nullptr) : -100;
+    if (rc == 0 && !pads_intact(y, M, g.N, g.cpad)) rc = -101;
     double num = 0, den = 0;
     for (int img = 0; img < g.nimg; ++img)
         for (int yy = 0; yy < g.H; ++yy)
@@ -270,7 +300,7 @@ static void run_entry(const Geo& g) {
                         for (int q = 0; q < 3; ++q)
                             for (int c = 0; c < C; ++c) want += w[((size_t)n * 9 + 3 * r + q) * C + c] * pixel(a, a2, g, img, yy - 1 + r, xx - 1 + q, c);
                     want += epilogue(g, bias, rowvec, res, row, n);
-                    const double dd = y[(size_t)row * g.N + n] - want;
+                    const double dd = y[(size_t)row * (g.N + g.cpad) + n] - want;
                     num += dd * dd;
                     den += want * want;
                 }
@@ -278,6 +308,7 @@ static void run_entry(const Geo& g) {
     char name[128];
     snprintf(name, sizeof(name), "entry point %dx%dx%d C=%d+%d N=%d%s%s%s", g.nimg, g.H, g.W, g.C1, g.C2, g.N, g.bias ? " bias" : "",
              g.rowvec ? " rowvec" : "", g.res ? " residual" : "");
+    tag(name, sizeof(name), g);
     verdict(name, rc, num, den, 2e-3);                   // the project's bound for a convolution (the form sits near 6e-4)
 }
 
@@ -329,6 +360,23 @@ int main() {
                 }
     // ... and all eight on one geometry (two sources, non-square, a row vector shared by two of the three images)
     for (e = 0; e < 8; ++e) run_entry(Geo{3, 4, 6, 64, 64, 40, (e & 1) != 0, (e & 2) != 0, (e & 4) != 0});
+    // the edges tests/winograd_case.py aims the GPU parity cases at, from this program's own double loops: rows_per_vec = W (the two
+    // rows of a tile take different vectors) and 3 (the two columns do), ldc > N with ldr != ldc above and below it, one tile per
+    // image under both, and two sources of different widths in both orders
+    for (long r : {6L, 3L, 1L}) {
+        run_output(Geo{3, 4, 6, 8, 0, 40, true, true, true, r});
+        run_entry(Geo{3, 4, 6, 72, 0, 40, true, true, true, r});
+    }
+    for (auto& pads : {std::pair<int, int>{8, 16}, {16, 0}, {0, 8}}) {
+        run_output(Geo{3, 4, 6, 8, 0, 40, true, true, true, 0, pads.first, pads.second});
+        run_entry(Geo{3, 4, 6, 72, 0, 40, true, true, true, 6, pads.first, pads.second});
+    }
+    run_output(Geo{3, 2, 2, 8, 0, 8, true, true, true, 2, 8, 0});
+    run_entry(Geo{3, 2, 2, 8, 0, 8, true, true, true, 3, 8, 16});
+    for (auto& c : {std::pair<int, int>{64, 128}, {128, 64}}) {
+        run_input(Geo{3, 4, 6, c.first, c.second, 8, false, false, false});
+        run_entry(Geo{3, 4, 6, c.first, c.second, 40, true, true, true, 3, 8, 0});
+    }
     run_refusals();
 #ifndef CHECK_WINOGRAD_REAL_GEMM
     if (n_gemm_bad) printf("the GEMM stage was handed %d description(s) that are not a plain batch of 16 FAIL\n", n_gemm_bad), ++n_bad;
